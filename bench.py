@@ -23,6 +23,21 @@ Workload (``--config``, default by world size; hspmv.dist.default_config):
   (the same matrix RCM-permuted, the reference's input ordering).
 ``--dry-run`` prints the partition plan without touching a GPU.
 
+A plain run does only what the headline needs: set up, W warm-up steps, the K
+timed steps, the outputs of ``--dump-outputs DIR`` if asked for, the JSON line
+(``value``, ``ms_per_step``, the ``roofline`` block from the same K launches).
+``--dump-outputs DIR`` writes the y the last timed step left -- this rank's
+rows, as the caller of the path receives them -- to ``DIR/y.npy``
+(``DIR/y_rank<r>.npy`` at N > 1) in the workload's dtype; all ranks together
+write at most 64 MB, a larger y as a fixed seeded sample of its entries in
+index order.  The matrix and x are seeded, so two runs with the same
+arguments compute the same thing.
+
+Every other leg below takes runs of its own and is measured only with
+``--full``: ``cold``, ``comm``, ``csr3_maps_plans``, ``scaling_reference``,
+``strong_scaling``, ``cpu_baseline``, ``cpu_c1`` and the ``check`` of y (a
+failing check exits 3); without it those fields are null.
+
 Extra fields on the line:
   roofline     one SpMV (the kernel launch(es) of a step), algorithmic bytes
                per SpMV / HIP-event-timed average over the timed region on
@@ -106,9 +121,16 @@ def parse():
     ap.add_argument("--nt", action="store_true", help="non-temporal matrix loads")
     ap.add_argument("--xcd-chunk", type=int, default=0,
                     help="workgroups per XCD turn (0 = the planner's choice, 1 = dispatch order)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the legs beside the headline: cold, comm, csr3_maps_plans, "
+                         "scaling_reference / strong_scaling, cpu_baseline, cpu_c1, and check y")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the y of the last timed step to DIR/y.npy (DIR/y_rank<r>.npy at "
+                         "N > 1), at most 64 MB in all")
     ap.add_argument("--cold-steps", type=int, default=20)
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="budget of the CPU-baseline sample (rank 0, N=1)")
+                    help="budget of the CPU-baseline sample (rank 0, N=1; with --full, as are "
+                         "--cold-steps and the --no-* switches below)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-plans", action="store_true",
                     help="skip the csr3_maps_plans legs (maps-driven CSR-3 plans)")
@@ -525,6 +547,30 @@ def overlapped_gather(args, A, shard, x, y, stream, device, info, world, chunks:
              "y_equal_to_plain_gather": ok}, ok)
 
 
+# ------------------------------------------------------------------ outputs
+
+DUMP_BUDGET_BYTES = 64 * 10**6  # all ranks together
+
+
+def dump_outputs(d: str, y, rank: int, world: int) -> dict:
+    """--dump-outputs: this rank's y (a host array, the last timed step's) as
+    DIR/y.npy, or DIR/y_rank<r>.npy at N > 1, in y's own dtype (float32 or
+    float64).  Each rank may write DUMP_BUDGET_BYTES / N; a larger y is
+    written as a sample of its entries, in index order, whose indices depend
+    only on the seed, the rank and y's length -- the same entries in every
+    run and every build."""
+    out = Path(d)
+    out.mkdir(parents=True, exist_ok=True)
+    keep = DUMP_BUDGET_BYTES // world // y.itemsize
+    sampled = y.size > keep
+    if sampled:
+        idx = np.sort(np.random.default_rng(20240 + rank).choice(y.size, size=keep, replace=False))
+        y = y[idx]
+    name = "y.npy" if world == 1 else f"y_rank{rank}.npy"
+    np.save(out / name, np.ascontiguousarray(y))
+    return {"file": name, "entries": int(y.size), "dtype": str(y.dtype), "sampled": bool(sampled)}
+
+
 # ------------------------------------------------------------------ main
 
 # Environment the ranks of a self-launched run get when the caller left it
@@ -637,12 +683,18 @@ def main():
     step_s = reduce_over_ranks(wall / args.steps, world, "max")
     ev_launch_s = ev0.elapsed_time(ev1) * 1e-3 / args.steps
 
+    # the y of the last timed step, before any other leg launches
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, y.cpu().numpy(), rank, world)
+
     # cold: evict the 256 MiB Infinity Cache before every launch by READING a
     # 512 MiB buffer (a read leaves no dirty lines whose write-back the SpMV
     # would then pay for)
-    flush = torch.ones(64 << 20, dtype=torch.float64, device="cuda")
+    full = args.full
+    flush = torch.ones(64 << 20, dtype=torch.float64, device="cuda") if full else None
     cold = []
-    for _ in range(args.cold_steps):
+    for _ in range(args.cold_steps if full else 0):
         flush.sum()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with leg_range("bench:headline_cold"):
@@ -655,16 +707,18 @@ def main():
     cold_s = reduce_over_ranks(float(np.median(cold)), world, "max") if cold else None
 
     # correctness property on the last y (no oracle in the product bench)
-    x_host = x.cpu().numpy()
-    ok, rel = hdist.checksum_ok(A, x_host, y.cpu().numpy())
-    ok_all = reduce_over_ranks(1.0 if ok else 0.0, world, "sum") == world
+    ok_all, rel = True, None
+    if full:
+        x_host = x.cpu().numpy()
+        ok, rel = hdist.checksum_ok(A, x_host, y.cpu().numpy())
+        ok_all = reduce_over_ranks(1.0 if ok else 0.0, world, "sum") == world
 
     # exchange step costs (reported, not in the step): y all-gather over RCCL,
     # and the halo exchange that replaces the x broadcast when x is
     # distributed like y (iterative use; point-to-point RCCL send/recv)
-    gather_ms = halo_ms = None
+    gather_ms = halo_ms = overlap = None
     halo_b = 0
-    if world > 1:
+    if world > 1 and full:
         times = []
         for _ in range(5):
             barrier(world)
@@ -700,14 +754,14 @@ def main():
     traffic = load_traffic(workload_key) if rank == 0 else None
 
     plans = None
-    if maps is not None and info["kernel_name"] == "csr3" and not args.no_plans:
+    if full and maps is not None and info["kernel_name"] == "csr3" and not args.no_plans:
         plans = csr3_maps_plans(args, A, maps, x, y, stream, local)
         ok_all = ok_all and reduce_over_ranks(
             1.0 if all(p["y_bitwise_equal_to_headline"] for p in plans.values()) else 0.0,
             world, "sum") == world
 
     sref = None
-    if world == 1 and cfg != hdist.default_config(2) and not args.no_scaling_ref:
+    if full and world == 1 and cfg != hdist.default_config(2) and not args.no_scaling_ref:
         sref = scaling_reference(args, stream)
         ok_all = ok_all and sref["check"]["pass"]
 
@@ -715,7 +769,7 @@ def main():
     # sharded run while the other ranks wait -- every N > 1 line is then a
     # self-contained scaling point (warm and cold efficiency)
     scal = None
-    if world > 1 and not args.no_scaling_ref:
+    if full and world > 1 and not args.no_scaling_ref:
         barrier(world)
         n1 = single_gpu_point(args, stream, cfg) if rank == 0 else None
         barrier(world)
@@ -726,7 +780,7 @@ def main():
         ok_all = reduce_over_ranks(1.0 if ok_all else 0.0, world, "sum") == world
 
     cpu = c1 = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(A, x_host, args.cpu_seconds)
         c1 = cpu_c1(max(0.2, 0.25 * args.cpu_seconds))
 
@@ -797,7 +851,9 @@ def main():
                                            if gather_ms is not None else round(gflops, 3)),
                      "iterative_gflops": (round(flops_step / (step_s + halo_ms * 1e-3) * 1e-9, 3)
                                           if halo_ms is not None else round(gflops, 3))},
-            "check": {"pass": bool(ok_all), "checksum_rel": rel},
+            "full": full,
+            "outputs": dumped,
+            "check": {"pass": bool(ok_all), "checksum_rel": rel} if full else None,
             "csr3_maps_plans": plans,
             "scaling_reference": sref,
             "strong_scaling": scal,

@@ -10,8 +10,8 @@ export PYTHONUNBUFFERED=1
 P=$R/gpurun_out/$TAG/pmc
 bash heterogeneous-spmv_amd/tools/host_info.sh gpurun_out/$TAG/host.txt
 # only the headline launches (+ the cold leg, last): no plan legs, no C4
-PB="python3 $R/bench.py --no-cpu --no-plans --no-scaling-ref --steps 50 --warmup 10 --cold-steps 10 $BARGS"
-timeout -k 10 300 python3 bench.py --no-cpu --no-plans --no-scaling-ref --steps 50 --warmup 10 --cold-steps 10 $BARGS > gpurun_out/$TAG/bench_pmc_plain.log 2>&1 || exit 1
+PB="python3 $R/bench.py --full --no-cpu --no-plans --no-scaling-ref --steps 50 --warmup 10 --cold-steps 10 $BARGS"
+timeout -k 10 300 $PB > $(dirname $P)/bench_pmc_plain.log 2>&1 || exit 1
 cd /tmp && export TMPDIR=/tmp
 echo "== rocprof RDREQ" && timeout -k 10 -s KILL 300 rocprofv3 --pmc TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_32B_sum --output-format csv -d $P/rdreq -o bench -- $PB > $R/gpurun_out/$TAG/rocprof_rdreq.log 2>&1 &&
 echo "== rocprof FETCH_SIZE" && timeout -k 10 -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $P/fetch -o bench -- $PB > $R/gpurun_out/$TAG/rocprof_fetch.log 2>&1 &&

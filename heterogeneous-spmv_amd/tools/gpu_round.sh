@@ -10,7 +10,8 @@
 #   gputest[:KEXPR]     pytest -m gpu (optionally -k KEXPR)
 #   tests:FILES[:KEXPR] pytest on the given test files (comma separated), gpu+cpu
 #   smoke               __graft_entry__.smoke()
-#   bench[:ARGS]        python bench.py ARGS (ARGS: commas become spaces)
+#   bench[:ARGS]        python bench.py ARGS (ARGS: commas become spaces; --full
+#                       for the legs beside the headline, here and below)
 #   rocprof[:ARGS]      rocprofv3 --kernel-trace --stats of bench.py ARGS
 #   rocprofleg[:ARGS]   the same with --marker-trace --kernel-rename: kernels
 #                       reported per bench leg (bench.py's roctx ranges)

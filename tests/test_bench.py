@@ -1,7 +1,8 @@
 """bench.py contract: the CPU-side dry run names the configuration each world
 size measures (C3 at N = 1, C4 strong scaling at N > 1) and its partition;
-on one GPU, one JSON line with the driver's keys, the roofline and
-cpu_baseline objects, and a passing y check (short run)."""
+on one GPU, one JSON line with the driver's keys and the roofline (a plain
+run: nothing else, and the y that --dump-outputs writes), and under --full
+the cpu_baseline and the other legs and a passing y check (short runs)."""
 import json
 import os
 import subprocess
@@ -156,7 +157,7 @@ def test_cpu_baseline_runs_in_its_own_process(tmp_path):
 @pytest.mark.gpu
 def test_bench_json_line_contract():
     env = dict(os.environ, PYTHONUNBUFFERED="1")
-    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "20", "--warmup", "3",
+    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--full", "--steps", "20", "--warmup", "3",
                           "--cold-steps", "2", "--cpu-seconds", "0.5"],
                          cwd=REPO, env=env, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -208,6 +209,57 @@ def test_bench_json_line_contract():
 
 
 @pytest.mark.gpu
+def test_plain_run_times_only_the_headline_and_dumps_y(tmp_path):
+    """Without --full the line carries the headline and its roofline and no
+    other leg; --dump-outputs writes the last timed step's y, which is the
+    SpMV of the seeded matrix and x.  C2 (1000 x 1000 Laplacian) keeps it
+    short."""
+    import oracle
+    from conftest import fp64_tol_ok
+    from hspmv import gen
+    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--config", "c2", "--steps", "5",
+                          "--warmup", "2", "--dump-outputs", str(tmp_path / "out")],
+                         cwd=REPO, env=dict(os.environ, PYTHONUNBUFFERED="1"),
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 5 and d["warmup"] == 2 and d["dtype"] == "f64"
+    assert d["unit"] == "GFLOP/s" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert abs(d["value"] - 2 * d["config"]["nnz"] / (d["ms_per_step"] * 1e-3) * 1e-9) < 1e-2 * d["value"]
+    assert 0 < d["roofline"]["frac"] < 1 and d["roofline"]["launch_us_events"] > 0
+    for k in ("cold", "check", "csr3_maps_plans", "scaling_reference", "strong_scaling",
+              "cpu_baseline", "cpu_c1"):
+        assert d[k] is None, k
+    assert d["outputs"] == {"file": "y.npy", "entries": 1_000_000, "dtype": "float64", "sampled": False}
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["y.npy"]
+    y = np.load(tmp_path / "out" / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (1_000_000,)
+    A = gen.laplace2d(1000, 1000)
+    x = gen.rand_x(A.n, 42)
+    y_ref = oracle.spmv(A.row_ptr, A.col_idx, A.val, x)
+    assert fp64_tol_ok(y, y_ref, oracle.abs_rowsum(A.row_ptr, A.col_idx, A.val, x))
+
+
+def test_dump_outputs_samples_a_large_y_within_the_budget(tmp_path):
+    """A y above the budget is written as the same seeded sample every time,
+    in index order; every rank's share of the 64 MB is 1 / N."""
+    sys.path.insert(0, str(REPO))
+    import bench
+    y = np.arange(3_000_000, dtype=np.float64)
+    info = bench.dump_outputs(str(tmp_path / "a"), y, 1, 4)
+    again = bench.dump_outputs(str(tmp_path / "b"), y, 1, 4)
+    got = np.load(tmp_path / "a" / "y_rank1.npy")
+    assert info == again and info["sampled"] is True and info["file"] == "y_rank1.npy"
+    assert got.dtype == np.float64 and got.nbytes == 16_000_000 == bench.DUMP_BUDGET_BYTES // 4
+    assert np.all(np.diff(got) > 0) and np.array_equal(got, np.load(tmp_path / "b" / "y_rank1.npy"))
+    small = bench.dump_outputs(str(tmp_path / "a"), y[:1000].astype(np.float32), 0, 1)
+    assert small == {"file": "y.npy", "entries": 1000, "dtype": "float32", "sampled": False}
+    assert np.array_equal(np.load(tmp_path / "a" / "y.npy"), y[:1000].astype(np.float32))
+
+
+@pytest.mark.gpu
 def test_bench_multi_rank_path_rehearsal_on_one_gpu(tmp_path):
     """bench.py's N > 1 code path (self-launched ranks, shards, x broadcast,
     barriers, max over ranks, y all-gather, halo exchange, rank-0 JSON line)
@@ -218,7 +270,7 @@ def test_bench_multi_rank_path_rehearsal_on_one_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["PYTHONUNBUFFERED"] = "1"
     # the plain command: bench.py starts its own launcher (self_launch)
-    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2",
+    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--full",
                           "--backend", "gloo", "--same-device", "--config", "c2",
                           "--steps", "10", "--warmup", "2", "--cold-steps", "2"],
                          cwd=REPO, env=env, capture_output=True, text=True, timeout=400)
@@ -253,7 +305,7 @@ def test_bench_eight_rank_orchestration_rehearsal_on_one_gpu(tmp_path):
     the strong_scaling block."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["PYTHONUNBUFFERED"] = "1"
-    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "8",
+    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "8", "--full",
                           "--backend", "gloo", "--same-device", "--config", "c2",
                           "--steps", "10", "--warmup", "2", "--cold-steps", "2"],
                          cwd=REPO, env=env, capture_output=True, text=True, timeout=600)

@@ -85,10 +85,10 @@ def test_library_partition_distinct_devices_csr3_uneven_ssr_splits():
 
 def test_bench_nccl_two_ranks():
     need(2)
-    # exactly the driver's command: no launcher, no extra environment
+    # the driver's command with every leg (--full): no launcher, no extra environment
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["PYTHONUNBUFFERED"] = "1"
-    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2",
+    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--full",
                           "--steps", "20", "--warmup", "3", "--cold-steps", "2"],
                          cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
