@@ -436,6 +436,7 @@ static int fill_info(hspmv_handle *h, hspmv_info *out) {
   out->csort_fixed_point = s.plan.kernel == kCsort && s.dp.cs.fixed ? 1 : 0;
   out->serial_order = 1;
   for (auto &sh : h->shards) out->serial_order &= sh.dp.serial_max == INT32_MAX ? 1 : 0;
+  out->row_slices = s.dp.sl_desc ? 1 : 0;
   if (s.plan.kernel == kCsort)
     for (int hh = 0; hh < 4; ++hh) out->csort_part_begin[hh] = s.csort_part_begin[hh];
   for (auto &sh : h->shards)

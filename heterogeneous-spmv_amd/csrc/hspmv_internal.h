@@ -31,6 +31,7 @@ struct DevCSR {
   // dictionaries were built for this shard
   bool has_xwin = false, has_xdict = false;
   bool has_xdict_tasks = false;  // x dictionaries built for packed CSR3 tasks
+  bool has_slices = false;       // ... and stored as row slices (DevPlan.sl_desc)
   int32_t n_slabs = 1;        // x slabs: the row kernel's passes (each sees ~nnz / n_slabs)
   int32_t task_waves = 4;     // CSR3 wave tasks per workgroup: 4 (8 with 8-task dictionary
                               // blocks); the SSR plan: ssr_waves() per super-super-row
@@ -60,6 +61,7 @@ struct Tuning {
   int deterministic = 0;    // 1: ordered row kernels (omp_spmv's order); 2: reproducible (fixed-point csort allowed)
   int serial_max = 0;       // A/B: the row kernels' serial bound (0: kSerialMax)
   int placement_trials = 0; // 0/1 off, K <= 8 array sets
+  int row_slices = 0;       // -1 off, 0 auto, 1 whenever eligible (hspmv_slices.cpp)
   int ssr_w = 0;            // SSR plan waves per workgroup (0: ssr_waves(); A/B)
   int ssr_align = -1;       // SSR plan wave cut: 2 row-granular nnz balance (-1: default), 0 super-rows, 1 aligned pieces
   // A/B only (diagnostic builds)
@@ -198,6 +200,17 @@ struct DevPlan {
   const int32_t *xd_blk = nullptr;
   const void *xd_runs = nullptr;
   int32_t xd_lds_bytes = 0;
+  // Row slices (hspmv_slices.cpp): the dictionary handle's matrix stored per
+  // 64-row wave task column-major, one lane per row (hspmv_slices,
+  // spmv_device.cuh).  sl_desc: {prefix, first row} per task and a closing
+  // pair ({padded slot columns, m}); slice t's values start at sl_val + 64 *
+  // prefix elements, its positions at sl_pos + 64 * prefix; sl_len: one
+  // length per row.  Set only when the launch runs the slice kernel.
+  const int32_t *sl_desc = nullptr;
+  const uint8_t *sl_len = nullptr;
+  const uint16_t *sl_pos = nullptr;
+  const void *sl_val = nullptr;
+  int32_t n_slices = 0;  // descriptors (= wave tasks, the empty ones included)
   // x slabs (irregular gathers, x larger than an XCD's L2): the columns are
   // cut into n_slabs equal ranges and the row kernel runs
   // once per slab over a slab-major copy of the matrix -- pass b reads rows
@@ -224,6 +237,7 @@ struct LaunchPlan {
   int32_t groups = 1;      // STREAM: 64-row groups per wave (next group's rp prefetched)
   int32_t carry = 0;       // STREAM/CSR3: rows start from y (x-slab passes after the first)
   bool lds_pad = false;     // STREAM: bank-padded product buffers (spmv_device.cuh lds_ix)
+  bool row_slices = false;  // STREAM/CSR3 with dictionaries: the lane-per-row slice kernel
   int64_t blocks = 0;
 };
 

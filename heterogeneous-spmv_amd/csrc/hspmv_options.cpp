@@ -49,6 +49,7 @@ int tuning_from_options(const hspmv_options *o, Tuning *t) {
   t->stream_waves = v.stream_waves;
   t->deterministic = v.deterministic;
   t->placement_trials = v.placement_trials;
+  t->row_slices = v.row_slices < 0 ? -1 : (v.row_slices > 0 ? 1 : 0);
   return HSPMV_OK;
 }
 
@@ -100,6 +101,7 @@ void tuning_from_env(Tuning *t) {
   geti("HSPMV_CONTIG", &t->contig);
   geti("HSPMV_XD_WAVES", &t->xd_waves);
   geti("HSPMV_XD_BPC", &t->xd_blocks_per_cu);
+  if (const char *e = getenv("HSPMV_ROW_SLICES")) t->row_slices = atoi(e) == 0 ? -1 : 1;
   geti("HSPMV_PF", &t->pf);
   geti("HSPMV_YNT", &t->y_nt);
   geti("HSPMV_NT", &t->nt);

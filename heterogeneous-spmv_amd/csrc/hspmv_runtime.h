@@ -6,6 +6,7 @@
 //   hspmv_tables.cpp       host planner tables: 16-bit columns, wave tasks,
 //                          x windows, x slabs, split rows, CSR-3 SSR tasks
 //   hspmv_xdict.cpp        block x dictionaries (+ hspmv_xdict_plan)
+//   hspmv_slices.cpp       row slices of dictionary handles (+ hspmv_slices_plan)
 //   hspmv_csort_build.cpp  column-sorted row blocks (csort.hip's tables)
 //   hspmv_multi.cpp        the row-range partition over devices, RCCL
 //   hspmv_api.cpp          the C ABI entry points
@@ -57,6 +58,14 @@ struct Shard {
   int xd_shape = 0;                  // 0 none, kStream (256-row blocks), kCsr3 (4 packed tasks)
   int64_t xd_entries = 0;            // x entries staged per SpMV (all blocks)
   int64_t xd_runs_n = 0;             // run records incl. sentinels
+  // row slices (build_slices): the slice kernel's streams, built with the
+  // dictionaries when the handle is eligible (hspmv_slices.cpp)
+  int32_t *d_sl_desc = nullptr;
+  uint8_t *d_sl_len = nullptr;
+  uint16_t *d_sl_pos = nullptr;
+  void *d_sl_val = nullptr;
+  int64_t sl_bytes = 0, sl_desc_n = 0, sl_padded = 0;  // device bytes, descriptors, sum of slice widths
+  bool owns_csr = false;             // d_rp / d_ci / d_val are this shard's own uploads
   int32_t *d_slab_rp = nullptr;      // x slabs (build_xslabs): per-slab row pointers,
   int32_t *d_slab_col = nullptr;     // slab-major columns and values
   void *d_slab_val = nullptr;
@@ -175,8 +184,47 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags);
 // Which row kernel the planner will pick for a shard with n_ssr
 // super-super-rows and (CSR-3) wave tasks.
 int kernel_for_tables(int64_t n_ssr, bool have_tasks, unsigned flags);
-int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int64_t n, int dtype,
-                unsigned flags, bool have_xwin);
+int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n,
+                int dtype, unsigned flags, bool have_xwin);
+// The dictionaries of the workgroups whose rows are [bs[b], bs[b+1]).
+struct XdPlan {
+  std::vector<int32_t> blk;  // nb + 1 record ranges
+  std::vector<int32_t> rec;  // {x_start, lds_off} per run, sentinel {0, entries} per block
+  std::vector<uint16_t> pos; // per nonzero: position in its block's staged x (0 for split rows)
+  std::vector<int32_t> total;  // entries per block
+  int64_t entries = 0, in_kernel_nnz = 0;
+  int32_t tmax = 0;
+};
+int xd_block_tasks(const Tuning &t, int task_waves);
+int64_t xdict_cap_entries(int dtype, const Tuning &t);
+// slices: the workgroups' LDS is the dictionary alone (the slice kernel)
+bool plan_xdict_for(const int32_t *rp, const int32_t *col, int kern, int64_t m,
+                    std::vector<int32_t> &tasks, int W, int32_t long_t, int64_t cap, int dtype,
+                    const Tuning &tune, bool slices, bool fill, XdPlan &P, int64_t *cut);
+
+// ---- hspmv_slices.cpp
+struct SliceCounts {
+  int64_t n_desc = 0, n_slices = 0;  // wave tasks, and those with rows
+  int64_t padded = 0;                // sum of the slices' widths (x 64 = padded entries)
+  int64_t max_rows = 0, max_len = 0;
+};
+struct SlicePlan {
+  std::vector<int32_t> desc;
+  std::vector<uint8_t> len;
+  std::vector<uint16_t> pos;
+  std::vector<char> val;
+  int64_t padded = 0;
+};
+// Row ranges of the wave tasks of `kern`: the CSR3 task table, or STREAM's 64-row groups.
+std::vector<int32_t> slice_starts(int kern, int64_t m, const std::vector<int32_t> &tasks);
+// HSPMV_SLICES_OK when a handle with these options and rows takes the slice
+// format (dictionaries permitting), else the first rule it fails.
+int slices_why(const Tuning &t, unsigned flags, int kern, int W, const int32_t *rp, int64_t m,
+               int64_t n, int dtype, const std::vector<int32_t> &starts, SliceCounts *out);
+void build_slices(const int32_t *rp, const uint16_t *pos, const void *val, int64_t m, int dtype,
+                  const std::vector<int32_t> &starts, SlicePlan &P);
+int upload_slices(Shard &s, const SlicePlan &P);
+void drop_slices(Shard &s);
 
 // ---- hspmv_csort_build.cpp
 int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,

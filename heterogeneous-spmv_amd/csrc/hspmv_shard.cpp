@@ -50,6 +50,10 @@ void free_shard(Shard &s, bool borrowed) {
   (void)hipFree(s.d_xwin);
   (void)hipFree(s.d_xd_blk);
   (void)hipFree(s.d_xd_runs);
+  (void)hipFree(s.d_sl_desc);
+  (void)hipFree(s.d_sl_len);
+  (void)hipFree(s.d_sl_pos);
+  (void)hipFree(s.d_sl_val);
   (void)hipFree(s.d_slab_rp);
   (void)hipFree(s.d_slab_col);
   (void)hipFree(s.d_slab_val);
@@ -109,6 +113,7 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
   s.A.row_ptr = s.d_rp;
   s.A.col_idx = s.d_ci;
   s.A.val = s.d_val;
+  s.owns_csr = true;
   if (mp && mp->n_ssr > 0) {
     const int64_t nssr = ssr1 - ssr0;
     const int64_t sr0 = mp->outer[ssr0], sr1 = mp->outer[ssr1];
@@ -200,6 +205,7 @@ static constexpr int kPlacementTrials = 0;
 int place_shard(Shard &s, int64_t n, int dtype) {
   int trials = s.tune.placement_trials > 0 ? std::min(8, s.tune.placement_trials) : kPlacementTrials;
   if (trials <= 1 || (s.plan.kernel != kStream && s.plan.kernel != kCsr3) || s.A.m == 0) return HSPMV_OK;
+  if (s.dp.sl_desc) return HSPMV_OK;  // row slices: the trial sets copy the CSR-order streams
   const size_t sv = dtype_size(dtype);
   const int64_t m = s.A.m, nnz = s.A.nnz;
   if ((double)nnz * (double)(sv + 4) + (double)m * (double)(sv + 4) + (double)n * (double)sv <=

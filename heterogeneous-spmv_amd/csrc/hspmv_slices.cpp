@@ -1,0 +1,235 @@
+// hspmv_slices.cpp -- row slices: the dictionary handles' matrix stored per
+// 64-row wave task column-major, for the lane-per-row kernel
+// (see hspmv_runtime.h for the split of the host runtime).
+#include <string.h>
+
+#include <algorithm>
+#include <cstddef>
+#include <thread>
+#include <vector>
+
+#include "hspmv_runtime.h"
+
+namespace hspmv {
+
+// Row slices.  A handle with block x dictionaries whose in-kernel rows are
+// all summed serially (<= kSerialMax / kSerialMaxF32 nonzeros) needs no
+// product buffer: lane i of the wave that owns a task can walk row i itself,
+// left to right, if the task's nonzeros are stored slot by slot ("sliced
+// ELL").  Per wave task s (<= 64 rows, w_s = its longest row) the format holds
+//   values     64 * w_s elements: slots in groups of 16 bytes per lane (2 fp64
+//              / 4 fp32 consecutive slots of the lane's row, lane-major inside
+//              the group: one wave load is 1 KiB contiguous), then the w_s mod
+//              2 (4) last slots as single 64-lane columns; 0 past a row's end;
+//   positions  the dictionary positions (plan_xdict's 16-bit positions) in
+//              groups of 4 per lane (8 bytes), then the w_s mod 4 last slots
+//              as single columns; 0 past a row's end;
+//   lengths    one uint8 per row;
+//   descriptor {prefix, first row} per task, prefix = sum of w over the
+//              earlier tasks: slot k of slice s starts at element 64 * (prefix
+//              + k) of both streams, so every slice is 128-byte aligned in
+//              both.  A closing pair {sum of w, m} bounds the last task.
+// Rows are padded to their slice's longest row only (no alignment slots), and
+// the kernel masks the padding by the row length.
+//
+// Eligible (slices_why == HSPMV_SLICES_OK): dictionaries over the CSR3
+// aligned plan's tasks or STREAM's 64-row groups, no split rows, every row
+// within the dtype's serial bound, and the slice format's bytes per SpMV not
+// above the CSR-order format's -- padded * (sv + 2) + m + 8 * (tasks + 1)
+// against nnz * (sv + 2) + 4 * (m + 1); the rest (run records, staged x, y) is
+// common.  A request for the chunked kernel's own knobs (HSPMV_U,
+// HSPMV_FLAG_PREFETCH, deterministic = 3) keeps that kernel.  Auto
+// (row_slices = 0) also asks for a matrix that streams from HBM, the
+// dictionaries' own rule.  The two rules about speed -- the bytes and the HBM
+// residence -- are auto's: row_slices = 1 takes every handle the kernel can
+// run (a small matrix whose boundary rows or short last slice pad it past
+// the CSR order's bytes: stencil27(21) pads 10 %), with the same y.
+
+std::vector<int32_t> slice_starts(int kern, int64_t m, const std::vector<int32_t> &tasks) {
+  if (kern == kCsr3) return tasks;
+  std::vector<int32_t> st;
+  for (int64_t r = 0; r < m; r += 64) st.push_back((int32_t)r);
+  if (st.empty()) st.push_back(0);
+  st.push_back((int32_t)m);
+  return st;
+}
+
+int slices_why(const Tuning &t, unsigned flags, int kern, int W, const int32_t *rp, int64_t m,
+               int64_t n, int dtype, const std::vector<int32_t> &starts, SliceCounts *out) {
+  SliceCounts c;
+  c.n_desc = (int64_t)starts.size() - 1;
+  for (int64_t s = 0; s < c.n_desc; ++s) {
+    const int32_t a = starts[(size_t)s], b = starts[(size_t)s + 1];
+    int32_t w = 0;
+    for (int32_t r = a; r < b; ++r) w = std::max(w, rp[r + 1] - rp[r]);
+    c.n_slices += b > a ? 1 : 0;
+    c.max_rows = std::max<int64_t>(c.max_rows, b - a);
+    c.max_len = std::max<int64_t>(c.max_len, w);
+    c.padded += w;
+  }
+  if (out) *out = c;
+  if (t.row_slices < 0) return HSPMV_SLICES_OFF;
+  if (t.x_dict < 0 || (flags & HSPMV_FLAG_NO_COL16)) return HSPMV_SLICES_NO_DICT;
+  if (kern == kCsr3) {
+    if (t.csr3_plan == HSPMV_CSR3_PLAN_PACKED || t.csr3_plan == HSPMV_CSR3_PLAN_SSR || W != 4)
+      return HSPMV_SLICES_SHAPE;
+  } else if (kern != kStream || ((flags >> 29) & 0x7u) > 1) {
+    return HSPMV_SLICES_SHAPE;
+  }
+  if (c.max_rows > 64) return HSPMV_SLICES_SHAPE;
+  if (((flags >> 16) & 0x1Fu) || (flags & HSPMV_FLAG_PREFETCH) ||
+      t.deterministic == HSPMV_DETERMINISTIC_SERIAL || t.serial_max > 0)
+    return HSPMV_SLICES_CHUNKED;
+  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
+  if (c.max_len > long_t) return HSPMV_SLICES_SPLIT_ROWS;
+  if (c.max_len > (dtype == HSPMV_F32 ? kSerialMaxF32 : kSerialMax)) return HSPMV_SLICES_LONG_ROW;
+  const double sv = (double)dtype_size(dtype);
+  const double nnz = (double)rp[m];
+  if (t.row_slices == 0 &&
+      64.0 * (double)c.padded * (sv + 2.0) + (double)m + 8.0 * (double)(c.n_desc + 1) >
+          nnz * (sv + 2.0) + 4.0 * (double)(m + 1))
+    return HSPMV_SLICES_BYTES;
+  if (t.row_slices == 0 &&
+      nnz * (sv + 4.0) + (double)m * (sv + 4.0) + (double)n * sv <= kMallResident)
+    return HSPMV_SLICES_RESIDENT;
+  return HSPMV_SLICES_OK;
+}
+
+// Element of slot k of lane i in a slice of width w that starts at element
+// `base`; G slots per group.
+static inline size_t slot_at(size_t base, int32_t w, int32_t k, int i, int G) {
+  const int32_t wg = w / G * G;
+  return k < wg ? base + (size_t)(k / G) * 64 * G + (size_t)i * G + (size_t)(k % G)
+                : base + (size_t)k * 64 + (size_t)i;
+}
+
+void build_slices(const int32_t *rp, const uint16_t *pos, const void *val, int64_t m, int dtype,
+                  const std::vector<int32_t> &starts, SlicePlan &P) {
+  const int64_t nd = (int64_t)starts.size() - 1;
+  const size_t sv = dtype_size(dtype);
+  const int G = 16 / (int)sv;
+  P.desc.assign(2 * (size_t)(nd + 1), 0);
+  int64_t pre = 0;
+  for (int64_t s = 0; s < nd; ++s) {
+    int32_t w = 0;
+    for (int32_t r = starts[(size_t)s]; r < starts[(size_t)s + 1]; ++r) w = std::max(w, rp[r + 1] - rp[r]);
+    P.desc[2 * (size_t)s] = (int32_t)pre;
+    P.desc[2 * (size_t)s + 1] = starts[(size_t)s];
+    pre += w;
+  }
+  P.desc[2 * (size_t)nd] = (int32_t)pre;
+  P.desc[2 * (size_t)nd + 1] = (int32_t)m;
+  P.padded = pre;
+  P.len.assign((size_t)std::max<int64_t>(m, 1), 0);
+  for (int64_t r = 0; r < m; ++r) P.len[(size_t)r] = (uint8_t)(rp[r + 1] - rp[r]);
+  P.pos.assign((size_t)std::max<int64_t>(64 * pre, 1), 0);
+  P.val.assign(sv * (size_t)std::max<int64_t>(64 * pre, 1), 0);
+  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, nd / 256));
+  std::vector<std::thread> th;
+  for (int t = 0; t < nt; ++t)
+    th.emplace_back([&, t]() {
+      for (int64_t s = nd * t / nt; s < nd * (t + 1) / nt; ++s) {
+        const int32_t a = starts[(size_t)s], b = starts[(size_t)s + 1];
+        const size_t base = 64 * (size_t)P.desc[2 * (size_t)s];
+        const int32_t w = P.desc[2 * (size_t)s + 2] - P.desc[2 * (size_t)s];
+        for (int32_t r = a; r < b; ++r)
+          for (int32_t k = 0; k < rp[r + 1] - rp[r]; ++k) {
+            const size_t src = (size_t)rp[r] + (size_t)k;
+            P.pos[slot_at(base, w, k, r - a, 4)] = pos[src];
+            memcpy(P.val.data() + sv * slot_at(base, w, k, r - a, G), (const char *)val + sv * src, sv);
+          }
+      }
+    });
+  for (auto &x : th) x.join();
+}
+
+int upload_slices(Shard &s, const SlicePlan &P) {
+  int rc;
+  if ((rc = dev_alloc(&s.d_sl_desc, 4 * P.desc.size(), &s.bytes))) return rc;
+  if ((rc = dev_alloc(&s.d_sl_len, P.len.size(), &s.bytes))) return rc;
+  if ((rc = dev_alloc(&s.d_sl_pos, 2 * P.pos.size(), &s.bytes))) return rc;
+  if ((rc = dev_alloc(&s.d_sl_val, P.val.size(), &s.bytes))) return rc;
+  HIP_TRY(hipMemcpy(s.d_sl_desc, P.desc.data(), 4 * P.desc.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s.d_sl_len, P.len.data(), P.len.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s.d_sl_pos, P.pos.data(), 2 * P.pos.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s.d_sl_val, P.val.data(), P.val.size(), hipMemcpyHostToDevice));
+  s.sl_bytes = (int64_t)(4 * P.desc.size() + P.len.size() + 2 * P.pos.size() + P.val.size());
+  s.sl_desc_n = (int64_t)P.desc.size() / 2 - 1;
+  s.sl_padded = P.padded;
+  return HSPMV_OK;
+}
+
+void drop_slices(Shard &s) {
+  for (void *p : {(void *)s.d_sl_desc, (void *)s.d_sl_len, (void *)s.d_sl_pos, s.d_sl_val})
+    if (p) (void)hipFree(p);
+  if (s.d_sl_desc) s.bytes -= s.sl_bytes;
+  s.d_sl_desc = nullptr;
+  s.d_sl_len = nullptr;
+  s.d_sl_pos = nullptr;
+  s.d_sl_val = nullptr;
+  s.sl_bytes = 0;
+  s.A.has_slices = false;
+}
+
+}  // namespace hspmv
+
+using namespace hspmv;
+
+extern "C" {
+
+int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt,
+                      int64_t *n_desc, int64_t *n_slices, int64_t *padded_entries, int32_t *why,
+                      int32_t *desc, uint8_t *len, uint16_t *pos, void *val) {
+  clear_error();
+  if (!n_desc || !n_slices || !padded_entries || !why) return set_error(HSPMV_E_INVALID, "NULL output");
+  *n_desc = *n_slices = *padded_entries = 0;
+  *why = HSPMV_SLICES_SHAPE;
+  int rc;
+  Tuning tune;
+  if ((rc = tuning_from_options(opt, &tune))) return rc;
+  const unsigned flags = opt ? opt->flags : 0u;
+  if ((rc = validate_host_csr(A, true))) return rc;
+  if ((rc = validate_host_maps(maps, A->m))) return rc;
+  std::vector<int32_t> tasks;
+  const bool csr3 = maps && maps->n_ssr > 0;
+  int waves = 4;
+  if (csr3) {
+    const std::vector<int32_t> inner(maps->inner, maps->inner + maps->n_sr + 1);
+    const std::vector<int32_t> outer(maps->outer, maps->outer + maps->n_ssr + 1);
+    build_tasks(A->row_ptr, A->m, &inner, &outer, flags, tune, tasks, &waves);
+  } else {
+    build_tasks(A->row_ptr, A->m, nullptr, nullptr, flags, tune, tasks, &waves);
+  }
+  const int W = xd_block_tasks(tune, waves);
+  const int kern = kernel_for_tables(csr3 ? maps->n_ssr : 0, !tasks.empty(), flags);
+  if ((kern != kStream && kern != kCsr3) || A->m == 0) return HSPMV_OK;
+  SliceCounts c;
+  *why = slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, A->dtype,
+                    slice_starts(kern, A->m, tasks), &c);
+  *n_desc = c.n_desc;
+  *n_slices = c.n_slices;
+  *padded_entries = 64 * c.padded;
+  if (*why != HSPMV_SLICES_OK) return HSPMV_OK;
+  XdPlan P;
+  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
+  const bool fill = desc || len || pos || val;
+  int64_t cut = 0;
+  if (!plan_xdict_for(A->row_ptr, A->col_idx, kern, A->m, tasks, W, long_t,
+                      xdict_cap_entries(A->dtype, tune), A->dtype, tune, true, fill, P, &cut)) {
+    *why = HSPMV_SLICES_NO_DICT;  // some block exceeds the LDS cap
+    return HSPMV_OK;
+  }
+  const std::vector<int32_t> starts = slice_starts(kern, A->m, tasks);  // after the occupancy cuts
+  slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, A->dtype, starts, &c);
+  *n_desc = c.n_desc;
+  if (!fill) return HSPMV_OK;
+  SlicePlan S;
+  build_slices(A->row_ptr, P.pos.data(), A->val, A->m, A->dtype, starts, S);
+  if (desc) memcpy(desc, S.desc.data(), 4 * S.desc.size());
+  if (len && A->m) memcpy(len, S.len.data(), (size_t)A->m);
+  if (pos && S.padded) memcpy(pos, S.pos.data(), 2 * (size_t)(64 * S.padded));
+  if (val && S.padded) memcpy(val, S.val.data(), dtype_size(A->dtype) * (size_t)(64 * S.padded));
+  return HSPMV_OK;
+}
+
+}  // extern "C"

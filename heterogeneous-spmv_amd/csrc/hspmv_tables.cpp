@@ -723,7 +723,7 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
   if (!s.h_tasks.empty()) s.h_xwin_t = xwin_table(rp, col, m, &s.h_tasks, s.tune);
   const int kern = kernel_for_tables(s.A.n_ssr, !s.h_tasks.empty(), flags);
   const bool have_xwin = kern == kCsr3 ? !s.h_xwin_t.empty() : !s.h_xwin.empty();
-  if ((rc = build_xdict(s, rp, col, m, n, dtype, flags, have_xwin))) return rc;
+  if ((rc = build_xdict(s, rp, col, val, m, n, dtype, flags, have_xwin))) return rc;
   if (s.xd_shape) {  // col_span_bits: the planner's gather-regularity hint
     s.h_xwin.clear();
     s.h_xwin_t.clear();
@@ -825,17 +825,42 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags) {
                        s.plan.waves_per_block == 4) ||
                       (s.xd_shape == kCsr3 && s.plan.kernel == kCsr3 && !s.h_tasks.empty() &&
                        s.plan.waves_per_block == s.A.task_waves);
-    if (fits) {
+    const double sv = (double)dtype_size(dtype);
+    if (fits && s.d_sl_desc) {
+      // row slices: the launch reads the slice-major streams, one length per
+      // row and one descriptor per task instead of the CSR-order streams and
+      // the row pointers; the CSR-order values of an owned matrix are freed
+      // (nothing this handle launches reads them)
+      s.dp.xd_blk = s.d_xd_blk;
+      s.dp.xd_runs = s.d_xd_runs;
+      s.dp.xd_lds_bytes = s.xd_lds_bytes;
+      s.dp.sl_desc = s.d_sl_desc;
+      s.dp.sl_len = s.d_sl_len;
+      s.dp.sl_pos = s.d_sl_pos;
+      s.dp.sl_val = s.d_sl_val;
+      s.dp.n_slices = (int32_t)s.sl_desc_n;
+      s.plan.row_slices = true;
+      if (s.owns_csr && s.d_val) {
+        (void)hipFree(s.d_val);
+        s.d_val = nullptr;
+        s.A.val = nullptr;
+        s.bytes -= (int64_t)(sv * (double)s.A.nnz);
+      }
+      s.c16_saved = (double)s.A.nnz * (sv + 4.0) + 4.0 * (double)(m + 1) -
+                    (64.0 * (double)s.sl_padded * (sv + 2.0) + (double)m + 8.0 * (double)(s.sl_desc_n + 1)) -
+                    4.0 * (double)(s.xd_runs_n * 2) - 4.0 * (double)s.plan.blocks -
+                    sv * (double)(s.xd_entries - s.x_entries);
+    } else if (fits) {
       s.dp.xd_blk = s.d_xd_blk;
       s.dp.xd_runs = s.d_xd_runs;
       s.dp.xd_lds_bytes = s.xd_lds_bytes;
       // index bytes: 2 instead of 4 per in-kernel nonzero, plus the tables;
       // x: the staged entries instead of the distinct columns
-      const double sv = (double)dtype_size(dtype);
       s.c16_saved = 2.0 * (double)(s.A.nnz - long_nnz) - 4.0 * (double)(s.xd_runs_n * 2) -
                     4.0 * (double)s.plan.blocks - sv * (double)(s.xd_entries - s.x_entries);
     } else {  // planned for another block shape: the kernels read the 32-bit columns
       s.A.col16 = nullptr;
+      drop_slices(s);
     }
   } else if (s.A.col16 && s.A.c16_mode == 2 &&
              (s.plan.kernel != s.c16g_shape || (s.plan.kernel == kCsr3 && s.h_tasks.empty()))) {

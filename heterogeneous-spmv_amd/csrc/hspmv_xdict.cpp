@@ -43,16 +43,6 @@ int kernel_for_tables(int64_t n_ssr, bool have_tasks, unsigned flags) {
   return kStream;
 }
 
-// The dictionaries of the workgroups whose rows are [bs[b], bs[b+1]).
-struct XdPlan {
-  std::vector<int32_t> blk;  // nb + 1 record ranges
-  std::vector<int32_t> rec;  // {x_start, lds_off} per run, sentinel {0, entries} per block
-  std::vector<uint16_t> pos; // per nonzero: position in its block's staged x (0 for split rows)
-  std::vector<int32_t> total;  // entries per block
-  int64_t entries = 0, in_kernel_nnz = 0;
-  int32_t tmax = 0;
-};
-
 // false when some block needs more than cap entries.
 bool plan_xdict(const int32_t *rp, const int32_t *col, const std::vector<int32_t> &bs,
                 int32_t long_t, int64_t cap, bool fill, XdPlan &P) {
@@ -185,13 +175,19 @@ int64_t xdict_cap_entries(int dtype, const Tuning &t) {
 constexpr int kXdBlocksPerCu = 6;
 constexpr int64_t kLdsPerCu = 160 * 1024, kLdsGranule = 1024;
 
-int64_t xd_target_entries(int dtype, const Tuning &t) {
-  const int bpc = t.xd_blocks_per_cu > 0 ? t.xd_blocks_per_cu : kXdBlocksPerCu;
+// The slice kernel's workgroups hold no product staging: 8 per CU (32 waves,
+// the most 64 VGPRs admit) leave each a 20 KiB dictionary -- the cap itself,
+// so the default cap cuts nothing and only a raised x_dict_cap does.
+constexpr int kXdBlocksPerCuSlices = 8;
+
+int64_t xd_target_entries(int dtype, const Tuning &t, bool slices) {
+  const int bpc = t.xd_blocks_per_cu > 0 ? t.xd_blocks_per_cu
+                                         : (slices ? kXdBlocksPerCuSlices : kXdBlocksPerCu);
   const int64_t sv = (int64_t)dtype_size(dtype);
   // product staging of the chunk plan_launch picks for >= 12 nonzeros per
   // row (pick_u: U = 4 fp64, 16 fp32), 4 waves (CSR3 product buffers are
   // never bank-padded: spmv_device.cuh wave_lds<U, false>)
-  const int64_t staging = 4 * 64 * (sv == 8 ? 4 : 16) * sv + 16;
+  const int64_t staging = slices ? 0 : 4 * 64 * (sv == 8 ? 4 : 16) * sv + 16;
   const int64_t per_block = (kLdsPerCu / bpc) / kLdsGranule * kLdsGranule;
   return std::max<int64_t>(0, (per_block - staging) / sv);
 }
@@ -233,14 +229,14 @@ int64_t split_xd_blocks(std::vector<int32_t> &tasks, const std::vector<int32_t> 
 // (The SSR plan's blocks are its super-super-rows: never cut.)
 bool plan_xdict_for(const int32_t *rp, const int32_t *col, int kern, int64_t m,
                     std::vector<int32_t> &tasks, int W, int32_t long_t, int64_t cap, int dtype,
-                    const Tuning &tune, bool fill, XdPlan &P, int64_t *cut) {
+                    const Tuning &tune, bool slices, bool fill, XdPlan &P, int64_t *cut) {
   *cut = 0;
   const bool cuts = kern == kCsr3 && W == 4 && tune.csr3_plan != HSPMV_CSR3_PLAN_SSR &&
                     tune.xd_blocks_per_cu >= 0;
   if (!plan_xdict(rp, col, xdict_blocks(kern, m, tasks, W), long_t, cap, fill && !cuts, P))
     return false;
   if (!cuts) return true;
-  *cut = split_xd_blocks(tasks, P.total, xd_target_entries(dtype, tune));
+  *cut = split_xd_blocks(tasks, P.total, xd_target_entries(dtype, tune, slices));
   if (*cut == 0 && !fill) return true;
   return plan_xdict(rp, col, xdict_blocks(kern, m, tasks, W), long_t, cap, fill, P);
 }
@@ -249,8 +245,8 @@ bool plan_xdict_for(const int32_t *rp, const int32_t *col, int kern, int64_t m,
 // row kernel's window table qualified): on C4's shard the per-wave windows
 // need no block barrier and were 7 % faster than the dictionaries
 // (53.8 vs 57.9 us, profiles/r01_ab_xdict.jsonl).
-int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int64_t n, int dtype,
-                unsigned flags, bool have_xwin) {
+int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n,
+                int dtype, unsigned flags, bool have_xwin) {
   s.xd_shape = 0;
   const int mode = s.tune.x_dict > 0 ? 1 : (s.tune.x_dict < 0 ? 0 : -1);  // -1 auto, 0 off, 1 on when it fits
   if (mode == 0 || (flags & HSPMV_FLAG_NO_COL16) || m == 0) return HSPMV_OK;
@@ -268,19 +264,34 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int6
   XdPlan P;
   // (cuts the task table only when the dictionaries are taken)
   std::vector<int32_t> tasks = s.h_tasks;
+  // row slices (hspmv_slices.cpp): decided from the rows and the options
+  // before the dictionaries are planned, which are then sized for workgroups
+  // without product staging
+  const bool slices = slices_why(s.tune, flags, kern, W, rp, m, n, dtype, slice_starts(kern, m, tasks),
+                                 nullptr) == HSPMV_SLICES_OK;
   if (!plan_xdict_for(rp, col, kern, m, tasks, W, long_t, xdict_cap_entries(dtype, s.tune), dtype,
-                      s.tune, true, P, &s.xd_cut))
+                      s.tune, slices, true, P, &s.xd_cut))
     return HSPMV_OK;
   if (mode < 0 && 2 * P.entries > P.in_kernel_nnz) return HSPMV_OK;  // too little reuse to pay
   s.h_tasks.swap(tasks);
   int rc;
-  if ((rc = dev_alloc(&s.d_c16, 2 * (size_t)std::max<int64_t>(nnz, 1), &s.bytes))) return rc;
+  if (slices) {
+    // the slice kernel reads the positions and values slice-major: only
+    // those are uploaded (the CSR-order values go when the launch is
+    // settled, build_plan_tables)
+    SlicePlan S;
+    build_slices(rp, P.pos.data(), val, m, dtype, slice_starts(kern, m, s.h_tasks), S);
+    if ((rc = upload_slices(s, S))) return rc;
+    s.A.has_slices = true;
+  } else {
+    if ((rc = dev_alloc(&s.d_c16, 2 * (size_t)std::max<int64_t>(nnz, 1), &s.bytes))) return rc;
+    if (nnz) HIP_TRY(hipMemcpy(s.d_c16, P.pos.data(), 2 * (size_t)nnz, hipMemcpyHostToDevice));
+  }
   if ((rc = dev_alloc(&s.d_xd_blk, 4 * P.blk.size(), &s.bytes))) return rc;
   if ((rc = dev_alloc(&s.d_xd_runs, 4 * P.rec.size(), &s.bytes))) return rc;
-  if (nnz) HIP_TRY(hipMemcpy(s.d_c16, P.pos.data(), 2 * (size_t)nnz, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(s.d_xd_blk, P.blk.data(), 4 * P.blk.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(s.d_xd_runs, P.rec.data(), 4 * P.rec.size(), hipMemcpyHostToDevice));
-  s.A.col16 = s.d_c16;
+  s.A.col16 = slices ? s.d_sl_pos : s.d_c16;  // the 16-bit position stream the launch reads
   s.A.cbase = nullptr;
   s.A.cplanes = nullptr;
   s.A.n_cplanes = 0;
@@ -330,8 +341,11 @@ int hspmv_xdict_plan_ex(const hspmv_csr *A, const hspmv_csr3_maps *maps, const h
   const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
   const bool fill = blk || runs || pos;
   int64_t cut = 0;
+  // (sized as a handle with these options would: for the slice kernel when eligible)
+  const bool slices = slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, A->dtype,
+                                 slice_starts(kern, A->m, tasks), nullptr) == HSPMV_SLICES_OK;
   if (!plan_xdict_for(A->row_ptr, A->col_idx, kern, A->m, tasks, W, long_t,
-                      std::min<int64_t>(cap_entries, 65536), A->dtype, tune, fill, P, &cut))
+                      std::min<int64_t>(cap_entries, 65536), A->dtype, tune, slices, fill, P, &cut))
     return HSPMV_OK;  // some block exceeds the cap: no dictionary (n_blocks = 0)
   *n_blocks = (int64_t)P.blk.size() - 1;
   *n_records = (int64_t)P.blk.back();

@@ -702,7 +702,226 @@ __global__ __launch_bounds__(W * 64) void hspmv_csr3(
 #endif
 }
 
+// ------------------------------------------------------------------ row slices
+//
+// The transposed (sliced-ELL) shape of the dictionary kernels, for handles
+// whose every row is summed serially anyway (hspmv_slices.cpp holds the
+// format and the eligibility rules).  A wave's task of <= 64 rows is stored
+// column-major: lane i owns row i, slot k of all 64 rows lies together, so
+// one load instruction brings 16 bytes of values (2 fp64 / 4 fp32
+// consecutive slots of the lane's row) or 8 bytes of positions (4 slots) per
+// lane, and the lane multiplies and adds its own row left to right -- the
+// order and rounding of the ordered sums, with no product buffer in LDS, no
+// wave_sync and no row pointers.  Slot k of a slice starts at element 64 * k
+// of the slice in both streams (groups and the trailing single columns
+// alike).  Slots past a row's end are masked by its length, never added.
+#ifndef HSPMV_SLICE_BATCH
+#define HSPMV_SLICE_BATCH 8  // slots per load batch (a multiple of 4)
+#endif
+
+struct Slices {
+  const int32_t *desc;  // {prefix, first row} per task, closed by {total, m}
+  const uint8_t *len;   // nonzeros per row
+  const uint16_t *pos;  // dictionary positions, 64 * prefix elements per slice start
+};
+
+typedef int32_t sl_i4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// Scalar (s_load) read of 16 bytes at p + byte_off, both wave-uniform.
+__device__ __forceinline__ sl_i4 sload_i128(const void *p, uint64_t byte_off) {
+  const uint64_t v = reinterpret_cast<uint64_t>(p) + byte_off;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  typedef __attribute__((address_space(4))) const sl_i4 ci128;
+  return *(ci128 *)(((uint64_t)hi << 32) | lo);
+}
+
+template <typename T, int B>
+struct SliceBatch {
+  T v[B];               // slot k0 + i of the lane's row
+  uint32_t pq[B / 2];   // positions of whole 4-slot groups, two per register
+  uint32_t ps[3];       // positions of the slice's last 1-3 slots (single columns)
+};
+
+// A whole batch: slots [k0, k0 + B) all lie in 16-byte value groups and
+// 8-byte position groups.  vb / pb: the slice's streams.
+template <typename T, bool NT, int B>
+__device__ __forceinline__ void slice_load_full(SliceBatch<T, B> &q, const gchar *vb, const gchar *pb,
+                                                int32_t k0, int lane) {
+  constexpr int G = 16 / (int)sizeof(T);
+  typedef T tv __attribute__((ext_vector_type(G)));
+  typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+  const gchar *vbb = vb + (uint64_t)(uint32_t)k0 * (kWave * sizeof(T));
+  const gchar *pbb = pb + (uint64_t)(uint32_t)k0 * (kWave * 2u);
+#pragma unroll
+  for (int j = 0; j < B / G; ++j) {
+    const tv t = ld_off<NT, tv>(vbb, (uint32_t)(j * kWave + lane) * 16u);
+#pragma unroll
+    for (int e = 0; e < G; ++e) q.v[j * G + e] = t[e];
+  }
+#pragma unroll
+  for (int g = 0; g < B / 4; ++g) {
+    const u2 t = ld_off<NT, u2>(pbb, (uint32_t)(g * kWave + lane) * 8u);
+    q.pq[2 * g] = t[0];
+    q.pq[2 * g + 1] = t[1];
+  }
+}
+
+// The slice's last, partial batch: slots [k0, w), w - k0 < B; whole groups
+// as above, the rest from the single columns.  Slots past w read as value 0
+// at position 0 (and are masked like every slot past a row's end).
+template <typename T, bool NT, int B>
+__device__ __forceinline__ void slice_load_tail(SliceBatch<T, B> &q, const gchar *vb, const gchar *pb,
+                                                int32_t k0, int32_t w, int lane) {
+  constexpr int G = 16 / (int)sizeof(T);
+  typedef T tv __attribute__((ext_vector_type(G)));
+  typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+  const gchar *vbb = vb + (uint64_t)(uint32_t)k0 * (kWave * sizeof(T));
+  const gchar *pbb = pb + (uint64_t)(uint32_t)k0 * (kWave * 2u);
+#pragma unroll
+  for (int i = 0; i < B; ++i) q.v[i] = T(0);
+#pragma unroll
+  for (int i = 0; i < B / 2; ++i) q.pq[i] = 0u;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) q.ps[i] = 0u;
+#pragma unroll
+  for (int j = 0; j < B / G; ++j) {
+    if (k0 + j * G + G <= w) {  // wave-uniform
+      const tv t = ld_off<NT, tv>(vbb, (uint32_t)(j * kWave + lane) * 16u);
+#pragma unroll
+      for (int e = 0; e < G; ++e) q.v[j * G + e] = t[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < G - 1; ++e)
+        if (k0 + j * G + e < w)
+          q.v[j * G + e] = ld_off<NT, T>(vbb, (uint32_t)((j * G + e) * kWave + lane) * (uint32_t)sizeof(T));
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < B / 4; ++g) {
+    if (k0 + 4 * g + 4 <= w) {
+      const u2 t = ld_off<NT, u2>(pbb, (uint32_t)(g * kWave + lane) * 8u);
+      q.pq[2 * g] = t[0];
+      q.pq[2 * g + 1] = t[1];
+    } else {
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+        if (k0 + 4 * g + r < w)
+          q.ps[r] = (uint32_t)ld_off<NT, uint16_t>(pbb, (uint32_t)((4 * g + r) * kWave + lane) * 2u);
+    }
+  }
+}
+
+// Adds the batch's slots to acc in slot order: the product rounded on its
+// own (-ffp-contract=off), then the add; a slot at or past the row's end
+// leaves acc as it is.  full: every position comes from pq.
+template <typename T, int B>
+__device__ __forceinline__ T slice_consume(T acc, const SliceBatch<T, B> &q, const T *xs, int32_t k0,
+                                           int32_t w, int32_t len, bool full) {
+  T xv[B];
+#pragma unroll
+  for (int i = 0; i < B; ++i) {
+    const int g = i / 4, r = i % 4;
+    const uint32_t packed = (q.pq[2 * g + r / 2] >> (16 * (r & 1))) & 0xffffu;
+    const uint32_t p = (full || k0 + 4 * g + 4 <= w) ? packed : q.ps[r < 3 ? r : 0];
+    xv[i] = xs[p];
+  }
+#pragma unroll
+  for (int i = 0; i < B; ++i) {
+    const T p = q.v[i] * xv[i];
+    acc = (k0 + i < len) ? acc + p : acc;
+  }
+  return acc;
+}
+
+// One workgroup = one dictionary block (four wave tasks, or a half block's
+// two and two empty ones), staged by stage_xdict exactly as in the chunked
+// kernels.  Each wave reads its slice's descriptor (one scalar load) and its
+// rows' lengths before the staging; after the barrier it walks the slot
+// columns in batches of B, the next batch's loads issued before the current
+// one is consumed.  LDS: the dictionary alone.
+template <typename T, bool NT, int B>
+__global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t xcd_chunk, int32_t y_nt,
+                                                    Slices sl, XDict xd, const T *__restrict__ val,
+                                                    const T *__restrict__ x, T *__restrict__ y) {
+  static_assert(B % 4 == 0 && B >= 4, "batches hold whole position groups");
+  extern __shared__ __attribute__((aligned(16))) unsigned char xdyn[];
+  const int wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t blk = xcd_chunk_remap(blockIdx.x, gridDim.x, xcd_chunk);
+  const int64_t t = blk * 4 + wid;
+  int32_t off = 0, w = 0, r0 = 0, nr = 0;
+  if (t < n_slices) {  // wave-uniform
+    const sl_i4 d = sload_i128(sl.desc, (uint64_t)t * 8u);
+    off = d[0];
+    r0 = d[1];
+    w = d[2] - d[0];
+    nr = d[3] - d[1];
+  }
+  int32_t len = 0;
+  if (lane < nr) len = (int32_t)sl.len[r0 + lane];
+  stage_xdict<T, 256>(reinterpret_cast<T *>(xdyn), x, xd, blk, threadIdx.x);
+  if (nr <= 0) return;
+  const T *xs = reinterpret_cast<const T *>(xdyn);
+  const gchar *vb = uniform_ptr(val + (int64_t)off * kWave);
+  const gchar *pb = uniform_ptr(sl.pos + (int64_t)off * kWave);
+  const int32_t wf = w & ~(B - 1);  // slots in whole batches
+  T acc = T(0);
+  SliceBatch<T, B> cur, nxt, tail;
+  int32_t k0 = 0;
+  if (wf > 0) slice_load_full<T, NT, B>(cur, vb, pb, 0, lane);
+  for (; k0 + 3 * B <= wf; k0 += 2 * B) {
+    slice_load_full<T, NT, B>(nxt, vb, pb, k0 + B, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    acc = slice_consume<T, B>(acc, cur, xs, k0, w, len, true);
+    __builtin_amdgcn_sched_barrier(0);
+    slice_load_full<T, NT, B>(cur, vb, pb, k0 + 2 * B, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    acc = slice_consume<T, B>(acc, nxt, xs, k0 + B, w, len, true);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (k0 + 2 * B <= wf) {
+    slice_load_full<T, NT, B>(nxt, vb, pb, k0 + B, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    acc = slice_consume<T, B>(acc, cur, xs, k0, w, len, true);
+    __builtin_amdgcn_sched_barrier(0);
+    cur = nxt;
+    k0 += B;
+  }
+  // cur: the last whole batch (at wf - B), not yet added
+  if (w > wf) slice_load_tail<T, NT, B>(tail, vb, pb, wf, w, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  if (wf > 0) acc = slice_consume<T, B>(acc, cur, xs, wf - B, w, len, true);
+  if (w > wf) acc = slice_consume<T, B>(acc, tail, xs, wf, w, len, false);
+  if constexpr ((HSPMV_DIAG & 256) != 0) {  // ablation: no y stores (kept live)
+    if (lane < nr && acc == T(12345.678)) y[r0 + lane] = acc;
+  } else if (lane < nr) {
+    if (y_nt)
+      __builtin_nontemporal_store(acc, y + r0 + lane);
+    else
+      y[r0 + lane] = acc;
+  }
+}
+
 // ------------------------------------------------------------------ launchers
+
+template <typename T>
+hipError_t launch_slices(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st) {
+  if (!dp.xd_blk || !dp.sl_len || !dp.sl_pos || !dp.sl_val || p.waves_per_block != 4 ||
+      p.blocks != ((int64_t)dp.n_slices + 3) / 4)
+    return hipErrorInvalidValue;  // the host built the slices for another block shape
+  const Slices sl{dp.sl_desc, dp.sl_len, dp.sl_pos};
+  const XDict xd{dp.xd_blk, reinterpret_cast<const int2 *>(dp.xd_runs)};
+  const unsigned dyn = (unsigned)dp.xd_lds_bytes + (unsigned)p.dyn_lds;
+  const T *val = static_cast<const T *>(dp.sl_val);
+  if (p.nontemporal)
+    hipLaunchKernelGGL((hspmv_slices<T, true, HSPMV_SLICE_BATCH>), dim3((unsigned)p.blocks), dim3(256), dyn, st,
+                       dp.n_slices, (uint32_t)p.xcd_chunk, (int32_t)p.y_nt, sl, xd, val, x, y);
+  else
+    hipLaunchKernelGGL((hspmv_slices<T, false, HSPMV_SLICE_BATCH>), dim3((unsigned)p.blocks), dim3(256), dyn, st,
+                       dp.n_slices, (uint32_t)p.xcd_chunk, (int32_t)p.y_nt, sl, xd, val, x, y);
+  return hipGetLastError();
+}
 
 inline ColSrc col_src(const DevCSR &A) {
   return ColSrc{A.col_idx, A.col16, A.cbase, A.cplanes, A.n_cplanes, A.cplane_words};
@@ -810,6 +1029,7 @@ hipError_t launch_rows_c(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p
 template <typename T>
 hipError_t launch_rows(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const T *x, T *y,
                        hipStream_t st) {
+  if (dp.sl_desc) return launch_slices<T>(dp, p, x, y, st);  // row slices of a dictionary handle
   if (dp.xd_blk) {
     if (!A.col16 || (p.kernel == kStream && p.groups != 1) ||
         (p.kernel == kCsr3 && (!dp.task_start || (p.waves_per_block != 4 && p.waves_per_block != 8))))

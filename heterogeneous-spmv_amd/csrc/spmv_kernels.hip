@@ -39,6 +39,14 @@
 //      sub-warp per row inside (8,12)-thread blocks, csrk.cu:185-319) and
 //      cuSpMV_2 (degenerate outer level).
 //
+//  * hspmv_slices<T, NT, B>       (STREAM / CSR3 handles with row slices)
+//      the transposed shape of the two kernels above for dictionary handles
+//      whose rows are all summed serially: the wave's 64-row task is stored
+//      slot-major (hspmv_slices.cpp), lane i multiplies and adds row i left
+//      to right out of 16-byte value and 8-byte position loads, B slots per
+//      batch, the next batch in flight.  Same bits, no product buffer, no
+//      row pointers (spmv_device.cuh "row slices").
+//
 //  * hspmv_csr_vector<T, L, NT>   (HSPMV_KERNEL_VECTOR)
 //      L lanes (a sub-wave, L | 64) per row, lanes stride the row's nonzeros
 //      with FMA, reduced by __shfl_xor inside the L-lane group.  Replaces
@@ -498,7 +506,8 @@ LaunchPlan plan_launch(const DevCSR &A, int dtype, unsigned flags, double rows_p
   // box, 112.4 -> 110.3 on another; slower everywhere else: C3 fp32 +14 %,
   // C4 +13 %, honeycomb +10 %, C2 +14 %; profiles/r02q_ab_c3_u.jsonl,
   // r02r_ab_pf.jsonl)
-  if (!p.prefetch && dtype == 1 && p.kernel == kCsr3 && A.has_xdict_tasks && !forced_u)
+  // (not the slice kernel, hspmv_slices: it has one pipeline of its own)
+  if (!p.prefetch && dtype == 1 && p.kernel == kCsr3 && A.has_xdict_tasks && !forced_u && !A.has_slices)
     p.prefetch = true;
   // Bank-padded product buffers (STREAM, no prefetch): when
   // the typical serially summed row is a multiple of 16 LDS words long

@@ -123,12 +123,16 @@ class Info(C.Structure):
                 ("heavy_group_frac", C.c_double),
                 # since 1.1
                 ("csort_fixed_point", C.c_int32), ("serial_order", C.c_int32),
-                ("csort_part_begin", C.c_int64 * 4)]
+                ("csort_part_begin", C.c_int64 * 4),
+                ("row_slices", C.c_int32), ("reserved1", C.c_int32)]
 
 
 CSR3_PLANS = {"auto": 0, "aligned": 1, "packed": 2, "ssr": 3}
 # hspmv_options.deterministic (HSPMV_DETERMINISTIC_*)
 DETERMINISTIC = {"any": 0, "ordered": 1, "reproducible": 2, "serial": 3}
+# hspmv_slices_plan's *why (HSPMV_SLICES_*)
+SLICES_WHY = {0: "ok", 1: "off", 2: "no_dict", 3: "shape", 4: "chunked", 5: "split_rows",
+              6: "long_row", 7: "bytes", 8: "resident"}
 CSR3_PLAN_NAMES = {0: None, 1: "aligned", 2: "packed", 3: "ssr", 4: "row_groups"}
 
 
@@ -142,12 +146,13 @@ class Options(C.Structure):
                 ("x_dict", C.c_int32), ("x_dict_cap", C.c_int32), ("x_slabs", C.c_int32),
                 ("col16_group", C.c_int32), ("csort", C.c_int32), ("csort_parts", C.c_int32),
                 ("csort_chunk_u", C.c_int32), ("stream_waves", C.c_int32),
-                ("deterministic", C.c_int32), ("placement_trials", C.c_int32)]
+                ("deterministic", C.c_int32), ("placement_trials", C.c_int32),
+                ("row_slices", C.c_int32)]
 
     # planner fields a caller may set by name (SpMV(..., options={...}))
     TUNABLE = ("csr3_plan", "task_nnz", "x_windows", "x_dict", "x_dict_cap", "x_slabs",
                "col16_group", "csort", "csort_parts", "csort_chunk_u", "stream_waves",
-               "deterministic", "placement_trials")
+               "deterministic", "placement_trials", "row_slices")
 
 
 def make_options(flags: int, tuning: dict | None, *, device: int = 0, stream=None,
@@ -219,6 +224,9 @@ SIGNATURES = {
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P]),
     "hspmv_xdict_plan": (C.c_int, [C.POINTER(Csr), C.POINTER(Csr3Maps), C.c_uint, C.c_int64,
                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P]),
+    "hspmv_slices_plan": (C.c_int, [C.POINTER(Csr), C.POINTER(Csr3Maps), C.POINTER(Options),
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "hspmv_alg_bytes": (C.c_double, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64]),
     "hspmv_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "hspmv_rccl_version": (C.c_int, [C.POINTER(C.c_int)]),

@@ -296,6 +296,35 @@ def xdict_plan(A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, kernel: str = "
     return blk, runs, pos[:A.nnz]
 
 
+def slices_plan(A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, kernel: str = "auto",
+                split: bool = True, options: Optional[dict] = None, fill: bool = True) -> dict:
+    """Row slices the library would build for A (hspmv_slices_plan): a dict
+    with ``why`` (a _lib.SLICES_WHY name; "ok" = eligible), ``n_desc``,
+    ``n_slices``, ``padded_entries`` and -- when eligible and ``fill`` --
+    ``desc`` ((n_desc + 1, 2) {prefix, first row}), ``len``, ``pos``, ``val``."""
+    cs = A.c_struct()
+    ms = maps.c_struct() if maps is not None else None
+    flags = _KERNELS[kernel] | (0 if split else _lib.FLAG_NO_SPLIT)
+    opt = _lib.make_options(flags, options)
+    nd, ns, pe, why = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+    L = lib()
+    args = (C.byref(cs), C.byref(ms) if ms is not None else None, C.byref(opt),
+            C.byref(nd), C.byref(ns), C.byref(pe), C.byref(why))
+    check(L.hspmv_slices_plan(*args, None, None, None, None), "slices_plan")
+    out = {"why": _lib.SLICES_WHY[why.value], "n_desc": nd.value, "n_slices": ns.value,
+           "padded_entries": pe.value}
+    if why.value != 0 or not fill:
+        return out
+    desc = np.empty((nd.value + 1, 2), np.int32)
+    rl = np.zeros(max(A.m, 1), np.uint8)
+    pos = np.zeros(max(pe.value, 1), np.uint16)
+    val = np.zeros(max(pe.value, 1), A.val.dtype)
+    check(L.hspmv_slices_plan(*args, _ptr(desc), _ptr(rl), _ptr(pos), _ptr(val)), "slices_plan")
+    out.update(desc=desc, len=rl[:A.m], pos=pos[:pe.value], val=val[:pe.value],
+               n_desc=nd.value)
+    return out
+
+
 def alg_bytes(m: int, n: int, nnz: int, dtype, n_ssr: int = 0, n_sr: int = 0) -> float:
     return float(lib().hspmv_alg_bytes(m, n, nnz, dtype_code(dtype), n_ssr, n_sr))
 

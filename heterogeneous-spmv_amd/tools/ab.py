@@ -31,7 +31,9 @@ from auto_regret import build  # noqa: E402  (sweep.build + the planner zoo)
 def load(path):
     h = C.CDLL(str(path))
     for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(h, name)
+        fn = getattr(h, name, None)
+        if fn is None:  # an older build (the parent of an A/B) lacks the newer entry points
+            continue
         fn.restype, fn.argtypes = res, args
     return h
 

@@ -48,7 +48,8 @@ extern "C" {
 /* 1.1: hspmv_options.deterministic = 2 (HSPMV_DETERMINISTIC_REPRODUCIBLE)
  * and 3 (HSPMV_DETERMINISTIC_SERIAL), hspmv_info.csort_fixed_point /
  * serial_order / csort_part_begin; hspmv_get_info frozen at the 1.0 layout
- * (HSPMV_INFO_SIZE_1_0). */
+ * (HSPMV_INFO_SIZE_1_0).  Also in 1.1 (appended, nothing moved):
+ * hspmv_options.row_slices, hspmv_info.row_slices, hspmv_slices_plan. */
 
 /* ---------------------------------------------------------------- status */
 #define HSPMV_OK 0
@@ -203,6 +204,12 @@ typedef struct {
   int64_t csort_part_begin[4]; /* CSORT (GPU 0): first column of column part
                                   h (h < csort_parts; part h ends where h + 1
                                   begins, the last at n); 0 past the parts  */
+  int32_t row_slices;       /* 1: the dictionary handle's matrix is stored as
+                               row slices and run by the lane-per-row kernel
+                               (hspmv_options.row_slices); kernel, x_dict and
+                               the other fields read as for the chunked kernel,
+                               format_bytes counts the slice format          */
+  int32_t reserved1;
 } hspmv_info;
 
 typedef struct hspmv_handle hspmv_handle;
@@ -346,6 +353,12 @@ typedef struct {
                              hspmv_info.serial_order)                      */
   int32_t placement_trials; /* array placements timed at creation (0/1
                                off, K <= 8; see hspmv_create_on_device)    */
+  int32_t row_slices;     /* row slices (hspmv_slices_plan): -1 off, 0 auto
+                             (eligible handles that stream from HBM and whose
+                             padded format moves no more bytes), 1 whenever
+                             the kernel can run the handle (the rules
+                             HSPMV_SLICES_BYTES and _RESIDENT are auto's).
+                             y is the same bit for bit                      */
 } hspmv_options;
 
 /* ---------------------------------------------------------------- handle */
@@ -523,6 +536,42 @@ int hspmv_xdict_plan_ex(const hspmv_csr *A, const hspmv_csr3_maps *maps, const h
 int hspmv_xdict_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, unsigned flags,
                      int64_t cap_entries, int64_t *n_blocks, int64_t *n_records,
                      int32_t *blk, int32_t *runs, uint16_t *pos);
+/* Row slices (host planner; hspmv_create builds the same arrays when it uses
+ * them, see hspmv_info.row_slices).  A dictionary handle whose rows are all
+ * short enough to be summed serially (<= 40 nonzeros, fp32 56) stores each
+ * wave task of <= 64 rows column-major, padded to the task's longest row w:
+ * lane i of the wave owns row i and adds its products left to right, the same
+ * operations in the same order as the chunked kernel.  Slot k of the slice
+ * whose descriptor is desc[2s] = prefix, desc[2s+1] = first row starts at
+ * element 64 * (prefix + k) of val and of pos; w = desc[2s+2] - prefix, rows =
+ * desc[2s+3] - first row (desc holds n_desc + 1 pairs).  Values: groups of 16
+ * bytes per lane (2 fp64 / 4 fp32 consecutive slots; element 64 G g + G i + e
+ * of the slice is slot G g + e of lane i), then the last w mod G slots as
+ * single columns (element 64 k + i); positions (hspmv_xdict_plan_ex's, of the
+ * same options) likewise in groups of 4.  Entries past a row's end are 0;
+ * len[r] is row r's length.  *why = HSPMV_SLICES_OK when a handle with these
+ * options takes the format, else the first rule that refuses it; n_slices
+ * counts the tasks that have rows, padded_entries = 64 * the sum of w.  Call
+ * with NULL arrays for the counts.  The test and diagnostic view of the
+ * format, like hspmv_xdict_plan_ex. */
+#define HSPMV_SLICES_OK 0
+#define HSPMV_SLICES_OFF 1        /* hspmv_options.row_slices < 0             */
+#define HSPMV_SLICES_NO_DICT 2    /* no block x dictionaries (off, or a block
+                                     exceeds the LDS cap)                     */
+#define HSPMV_SLICES_SHAPE 3      /* not 64-row wave tasks, four per workgroup:
+                                     the packed or SSR CSR-3 plan, VECTOR,
+                                     CSORT, STREAM with several groups per wave */
+#define HSPMV_SLICES_CHUNKED 4    /* HSPMV_U, HSPMV_FLAG_PREFETCH or
+                                     deterministic = 3 ask for the chunked kernel */
+#define HSPMV_SLICES_SPLIT_ROWS 5 /* a row over 4096 nonzeros                 */
+#define HSPMV_SLICES_LONG_ROW 6   /* a row over the dtype's serial bound      */
+#define HSPMV_SLICES_BYTES 7      /* auto: the padded format would move more
+                                     bytes per SpMV than the CSR-order format */
+#define HSPMV_SLICES_RESIDENT 8   /* auto: the matrix is served from the
+                                     Infinity Cache (<= 192 MiB)              */
+int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt,
+                      int64_t *n_desc, int64_t *n_slices, int64_t *padded_entries, int32_t *why,
+                      int32_t *desc, uint8_t *len, uint16_t *pos, void *val);
 double hspmv_alg_bytes(int64_t m, int64_t n, int64_t nnz, int dtype,
                        int64_t n_ssr, int64_t n_sr);
 int hspmv_device_count(int *count);
