@@ -7,7 +7,6 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
-#include <thread>
 #include <vector>
 
 #include "hspmv_runtime.h"
@@ -86,8 +85,8 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
                     (dtype == HSPMV_F32 ? U % 2 == 0 : U % 4 == 0);
   const int64_t C = 64 * U;
   const size_t sv = dtype_size(dtype);
-  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX
-                         : (s.tune.csort_long > 0 ? s.tune.csort_long : kLongRow);
+  const int32_t long_t =
+      s.tune.csort_long > 0 && !(flags & HSPMV_FLAG_NO_SPLIT) ? s.tune.csort_long : split_threshold(flags);
   const int64_t nb0 = std::max<int64_t>(1, (int64_t)cus * bpc / H);
   // Column parts: [pb[h], pb[h+1]).  Equal widths, or (Tuning.csort_balance
   // >= 0, the default) boundaries at equal shares of the parts' COST, each
@@ -214,13 +213,7 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   // [h][r]: row r's in-kernel nonzeros in part h, then its partition weight
   std::vector<int32_t> cnt((size_t)(H * m), 0);
   std::vector<int64_t> tot_part((size_t)H, 0);
-  const int ntc = (int)std::max<int64_t>(1, std::min<int64_t>(16, m / 65536));
-  auto par_rows = [&](auto &&body) {
-    std::vector<std::thread> th;
-    for (int t = 0; t < ntc; ++t) th.emplace_back([&, t]() { body(t, m * t / ntc, m * (t + 1) / ntc); });
-    for (auto &x : th) x.join();
-  };
-  par_rows([&](int, int64_t r0, int64_t r1) {
+  parallel_ranges(m, 65536, [&](int64_t r0, int64_t r1, int) {
     for (int64_t r = r0; r < r1; ++r) {
       if (rp[r + 1] - rp[r] > long_t) continue;
       for (int32_t k = rp[r]; k < rp[r + 1]; ++k) ++cnt[(size_t)(part_of(col[k]) * m + r)];
@@ -244,7 +237,7 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
       cspan[(size_t)h] = tot_part[(size_t)h] ? (double)C * (double)(pb[(size_t)h + 1] - pb[(size_t)h]) *
                                                    (double)nb0 / (double)tot_part[(size_t)h]
                                              : 0.0;
-    par_rows([&](int, int64_t r0, int64_t r1) {
+    parallel_ranges(m, 65536, [&](int64_t r0, int64_t r1, int) {
       std::vector<int32_t> cs;
       std::vector<int32_t> crowded((size_t)H);
       for (int64_t r = r0; r < r1; ++r) {
@@ -339,7 +332,6 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   std::vector<std::vector<CsEnt>> ents((size_t)G);
   std::vector<int64_t> nchunks((size_t)G, 0);
   std::vector<int32_t> nslots((size_t)G, 0);
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, G / 4));
   std::atomic<bool> too_big{false};
   auto chunk_walk = [&](const std::vector<CsEnt> &E, auto &&emit) {
     // chunks of C entries, closed early when the span would pass 65535
@@ -355,32 +347,27 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
     }
     return cnt_;
   };
-  {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t)
-      th.emplace_back([&, t]() {
-        for (int64_t b = t; b < G; b += nt) {
-          const int h = (int)(b % H);
-          const int32_t r0 = wg_rows[(size_t)(2 * b)], r1 = wg_rows[(size_t)(2 * b + 1)];
-          const int32_t nr = r1 - r0;
-          auto &E = ents[(size_t)b];
-          for (int32_t r = r0; r < r1; ++r) {
-            if (rp[r + 1] - rp[r] > long_t) continue;
-            for (int32_t k = rp[r]; k < rp[r + 1]; ++k)
-              if (part_of(col[k]) == h) E.push_back({(uint32_t)col[k], (uint32_t)(r - r0), (uint32_t)k});
-          }
-          const auto &sl = wg_sl[(size_t)b];
-          for (size_t v = 0; v < sl.size(); ++v)
-            for (uint32_t k : slice_k[(size_t)sl[v]])
-              E.push_back({(uint32_t)col[k], (uint32_t)(nr + (int32_t)v), k});
-          std::sort(E.begin(), E.end());
-          nslots[(size_t)b] = nr + (int32_t)sl.size() + 1;  // + the dummy slot
-          if (nslots[(size_t)b] > 65536 || ((int64_t)nslots[(size_t)b] + 1) * slot_bytes > lds_max) too_big = true;
-          nchunks[(size_t)b] = chunk_walk(E, [](int64_t, uint32_t, int64_t, int64_t) {});
-        }
-      });
-    for (auto &x : th) x.join();
-  }
+  parallel_ranges(G, 4, [&](int64_t b0, int64_t b1, int) {
+    for (int64_t b = b0; b < b1; ++b) {
+      const int h = (int)(b % H);
+      const int32_t r0 = wg_rows[(size_t)(2 * b)], r1 = wg_rows[(size_t)(2 * b + 1)];
+      const int32_t nr = r1 - r0;
+      auto &E = ents[(size_t)b];
+      for (int32_t r = r0; r < r1; ++r) {
+        if (rp[r + 1] - rp[r] > long_t) continue;
+        for (int32_t k = rp[r]; k < rp[r + 1]; ++k)
+          if (part_of(col[k]) == h) E.push_back({(uint32_t)col[k], (uint32_t)(r - r0), (uint32_t)k});
+      }
+      const auto &sl = wg_sl[(size_t)b];
+      for (size_t v = 0; v < sl.size(); ++v)
+        for (uint32_t k : slice_k[(size_t)sl[v]])
+          E.push_back({(uint32_t)col[k], (uint32_t)(nr + (int32_t)v), k});
+      std::sort(E.begin(), E.end());
+      nslots[(size_t)b] = nr + (int32_t)sl.size() + 1;  // + the dummy slot
+      if (nslots[(size_t)b] > 65536 || ((int64_t)nslots[(size_t)b] + 1) * slot_bytes > lds_max) too_big = true;
+      nchunks[(size_t)b] = chunk_walk(E, [](int64_t, uint32_t, int64_t, int64_t) {});
+    }
+  });
   if (too_big) return HSPMV_OK;
   std::vector<int32_t> blk_c((size_t)G + 1, 0), blk_v((size_t)G + 1, 0), vslice;
   int64_t tot_chunks = 0;
@@ -419,133 +406,128 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   const bool stats = tn.csort_trace == 1;
   std::vector<int64_t> wst(stats ? (size_t)(kWgStats * G) : 0, 0);
   const int sec_shift = dtype == HSPMV_F32 ? 3 : 2;  // x entries per 32-byte sector: 8 / 4
-  {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t)
-      th.emplace_back([&, t]() {
-        for (int64_t b = t; b < G; b += nt) {
-          auto &E = ents[(size_t)b];
-          const uint32_t dummy = (uint32_t)(nslots[(size_t)b] - 1);
-          const int32_t br0 = wg_rows[(size_t)(2 * b)], bnr = wg_rows[(size_t)(2 * b + 1)] - br0;
-          const auto &bsl = wg_sl[(size_t)b];
-          auto row_of = [&](uint32_t slot) -> int64_t {  // source row of a slot (fixed-point scale)
-            return (int32_t)slot < bnr ? (int64_t)br0 + slot : slice_row(bsl[slot - bnr]);
-          };
-          const int64_t cfirst = blk_c[(size_t)b];
-          // entry q of a chunk (lane q % 64, u = q / 64) is stored at q, or,
-          // for 16-byte loads, interleaved so that one load brings the lane
-          // entries u, u+1 (fp32 records, fp64 values) or u..u+3 (fp64 indices)
-          auto at = [&](int64_t q, int per) -> int64_t {
-            if (!wide) return q;
-            const int64_t u = q / 64, lane = q % 64;
-            return (u / per) * (64 * per) + lane * per + (u % per);
-          };
-          std::vector<CsEnt> tmp;
-          uint32_t sl64[64];
-          chunk_walk(E, [&](int64_t ci, uint32_t c0, int64_t i, int64_t j) {
-            const int64_t ch = cfirst + ci;
-            // Same-slot lanes in one instruction serialise the LDS atomics:
-            // an RCM ordering puts a hub row's entries on contiguous columns,
-            // so column order can give one instruction 64 lanes of one row
-            // (RCM power-law: a few workgroups with ~100 K serialised lanes
-            // set the launch's tail, 204 vs 108 us).  Such chunks are stored
-            // sorted by slot instead and flagged (bit 31 of the base): the
-            // kernel sums each instruction's runs first (segmented scan).
-            const CsEnt *src = E.data() + i;
-            bool seg = false;
-            if (tn.csort_seg != 0) {
-              int64_t extra = 0;
-              for (int64_t g = i; g < j; g += 64) {
-                const int64_t e = std::min(j, g + 64);
-                for (int64_t t = g; t < e; ++t) sl64[t - g] = E[(size_t)t].slot;
-                std::sort(sl64, sl64 + (e - g));
-                int run = 1, mx = 1;
-                for (int64_t t = 1; t < e - g; ++t) {
-                  run = sl64[t] == sl64[t - 1] ? run + 1 : 1;
-                  mx = std::max(mx, run);
-                }
-                extra += mx - 1;
-              }
-              const int64_t lim = tn.csort_seg_extra > 0 ? tn.csort_seg_extra : kCsortSegExtra;
-              if (extra > lim || tn.csort_seg == 2) {
-                // the crowded rows (>= kCsortSegHeavy entries in this chunk)
-                // first, slot-sorted, in column order within each: their runs
-                // are contiguous columns (coalesced gathers); the other
-                // entries after them, still in column order
-                std::vector<std::pair<uint32_t, int32_t>> cnt_s;
-                cnt_s.reserve((size_t)(j - i));
-                for (int64_t t = i; t < j; ++t) cnt_s.push_back({E[(size_t)t].slot, 0});
-                std::sort(cnt_s.begin(), cnt_s.end());
-                std::vector<uint32_t> heavy;
-                for (size_t t = 0; t < cnt_s.size();) {
-                  size_t e = t;
-                  while (e < cnt_s.size() && cnt_s[e].first == cnt_s[t].first) ++e;
-                  if ((int64_t)(e - t) >= kCsortSegHeavy || tn.csort_seg == 2) heavy.push_back(cnt_s[t].first);
-                  t = e;
-                }
-                auto is_heavy = [&](uint32_t sl) { return std::binary_search(heavy.begin(), heavy.end(), sl); };
-                tmp.clear();
-                for (int64_t t = i; t < j; ++t)
-                  if (is_heavy(E[(size_t)t].slot)) tmp.push_back(E[(size_t)t]);
-                std::stable_sort(tmp.begin(), tmp.end(), [](const CsEnt &a, const CsEnt &b) { return a.slot < b.slot; });
-                for (int64_t t = i; t < j; ++t)
-                  if (!is_heavy(E[(size_t)t].slot)) tmp.push_back(E[(size_t)t]);
-                src = tmp.data();
-                seg = true;
-                n_seg.fetch_add(1, std::memory_order_relaxed);
-              }
+  parallel_ranges(G, 4, [&](int64_t b0, int64_t b1, int) {
+    for (int64_t b = b0; b < b1; ++b) {
+      auto &E = ents[(size_t)b];
+      const uint32_t dummy = (uint32_t)(nslots[(size_t)b] - 1);
+      const int32_t br0 = wg_rows[(size_t)(2 * b)], bnr = wg_rows[(size_t)(2 * b + 1)] - br0;
+      const auto &bsl = wg_sl[(size_t)b];
+      auto row_of = [&](uint32_t slot) -> int64_t {  // source row of a slot (fixed-point scale)
+        return (int32_t)slot < bnr ? (int64_t)br0 + slot : slice_row(bsl[slot - bnr]);
+      };
+      const int64_t cfirst = blk_c[(size_t)b];
+      // entry q of a chunk (lane q % 64, u = q / 64) is stored at q, or,
+      // for 16-byte loads, interleaved so that one load brings the lane
+      // entries u, u+1 (fp32 records, fp64 values) or u..u+3 (fp64 indices)
+      auto at = [&](int64_t q, int per) -> int64_t {
+        if (!wide) return q;
+        const int64_t u = q / 64, lane = q % 64;
+        return (u / per) * (64 * per) + lane * per + (u % per);
+      };
+      std::vector<CsEnt> tmp;
+      uint32_t sl64[64];
+      chunk_walk(E, [&](int64_t ci, uint32_t c0, int64_t i, int64_t j) {
+        const int64_t ch = cfirst + ci;
+        // Same-slot lanes in one instruction serialise the LDS atomics:
+        // an RCM ordering puts a hub row's entries on contiguous columns,
+        // so column order can give one instruction 64 lanes of one row
+        // (RCM power-law: a few workgroups with ~100 K serialised lanes
+        // set the launch's tail, 204 vs 108 us).  Such chunks are stored
+        // sorted by slot instead and flagged (bit 31 of the base): the
+        // kernel sums each instruction's runs first (segmented scan).
+        const CsEnt *src = E.data() + i;
+        bool seg = false;
+        if (tn.csort_seg != 0) {
+          int64_t extra = 0;
+          for (int64_t g = i; g < j; g += 64) {
+            const int64_t e = std::min(j, g + 64);
+            for (int64_t t = g; t < e; ++t) sl64[t - g] = E[(size_t)t].slot;
+            std::sort(sl64, sl64 + (e - g));
+            int run = 1, mx = 1;
+            for (int64_t t = 1; t < e - g; ++t) {
+              run = sl64[t] == sl64[t - 1] ? run + 1 : 1;
+              mx = std::max(mx, run);
             }
-            cbase[(size_t)ch] = (int32_t)(c0 | (seg ? 0x80000000u : 0u));
-            const int64_t ne = j - i;  // lanes >= ne: padding (gathers x[base])
-            if (stats) {
-              int64_t *w = wst.data() + kWgStats * b;
-              w[2] += 1;
-              w[3] += j - i;
-              w[6] += seg ? 1 : 0;
-              for (int64_t g = 0; g < C; g += 64) {  // one gather instruction
-                uint32_t sec[64];
-                for (int64_t q = 0; q < 64; ++q)
-                  sec[q] = (g + q < ne ? src[g + q].col : c0) >> sec_shift;
-                for (int64_t q = 0; q < 64; q += 4) {  // the L1 serves each quad on its own
-                  int d = 1;
-                  for (int t = 1; t < 4; ++t) {
-                    bool seen = false;
-                    for (int t2 = 0; t2 < t; ++t2) seen |= sec[q + t] == sec[q + t2];
-                    d += seen ? 0 : 1;
-                  }
-                  w[4] += d;
-                }
-                std::sort(sec, sec + 64);
-                w[5] += (int64_t)(std::unique(sec, sec + 64) - sec);
-              }
+            extra += mx - 1;
+          }
+          const int64_t lim = tn.csort_seg_extra > 0 ? tn.csort_seg_extra : kCsortSegExtra;
+          if (extra > lim || tn.csort_seg == 2) {
+            // the crowded rows (>= kCsortSegHeavy entries in this chunk)
+            // first, slot-sorted, in column order within each: their runs
+            // are contiguous columns (coalesced gathers); the other
+            // entries after them, still in column order
+            std::vector<std::pair<uint32_t, int32_t>> cnt_s;
+            cnt_s.reserve((size_t)(j - i));
+            for (int64_t t = i; t < j; ++t) cnt_s.push_back({E[(size_t)t].slot, 0});
+            std::sort(cnt_s.begin(), cnt_s.end());
+            std::vector<uint32_t> heavy;
+            for (size_t t = 0; t < cnt_s.size();) {
+              size_t e = t;
+              while (e < cnt_s.size() && cnt_s[e].first == cnt_s[t].first) ++e;
+              if ((int64_t)(e - t) >= kCsortSegHeavy || tn.csort_seg == 2) heavy.push_back(cnt_s[t].first);
+              t = e;
             }
-            for (int64_t q = 0; q < C; ++q) {
-              const int64_t o = ch * C + at(q, dtype == HSPMV_F32 ? 2 : 4);
-              const int64_t ov = ch * C + at(q, 2);
-              uint32_t ix = dummy << 16;  // padding: 0 * x[base] into the dummy slot
-              if (dtype == HSPMV_F32) {
-                uint32_t vb = 0;
-                if (q < ne) {
-                  const CsEnt &e = src[q];
-                  ix = (e.slot << 16) | (e.col - c0);
-                  vb = value_f32(e.k, row_of(e.slot));
-                }
-                rec[(size_t)o] = ((uint64_t)vb << 32) | ix;
-              } else {
-                if (q < ne) {
-                  const CsEnt &e = src[q];
-                  ix = (e.slot << 16) | (e.col - c0);
-                  val64[(size_t)ov] = value_f64(e.k, row_of(e.slot));
-                }
-                idx[(size_t)o] = ix;
+            auto is_heavy = [&](uint32_t sl) { return std::binary_search(heavy.begin(), heavy.end(), sl); };
+            tmp.clear();
+            for (int64_t t = i; t < j; ++t)
+              if (is_heavy(E[(size_t)t].slot)) tmp.push_back(E[(size_t)t]);
+            std::stable_sort(tmp.begin(), tmp.end(), [](const CsEnt &a, const CsEnt &b) { return a.slot < b.slot; });
+            for (int64_t t = i; t < j; ++t)
+              if (!is_heavy(E[(size_t)t].slot)) tmp.push_back(E[(size_t)t]);
+            src = tmp.data();
+            seg = true;
+            n_seg.fetch_add(1, std::memory_order_relaxed);
+          }
+        }
+        cbase[(size_t)ch] = (int32_t)(c0 | (seg ? 0x80000000u : 0u));
+        const int64_t ne = j - i;  // lanes >= ne: padding (gathers x[base])
+        if (stats) {
+          int64_t *w = wst.data() + kWgStats * b;
+          w[2] += 1;
+          w[3] += j - i;
+          w[6] += seg ? 1 : 0;
+          for (int64_t g = 0; g < C; g += 64) {  // one gather instruction
+            uint32_t sec[64];
+            for (int64_t q = 0; q < 64; ++q)
+              sec[q] = (g + q < ne ? src[g + q].col : c0) >> sec_shift;
+            for (int64_t q = 0; q < 64; q += 4) {  // the L1 serves each quad on its own
+              int d = 1;
+              for (int t = 1; t < 4; ++t) {
+                bool seen = false;
+                for (int t2 = 0; t2 < t; ++t2) seen |= sec[q + t] == sec[q + t2];
+                d += seen ? 0 : 1;
               }
+              w[4] += d;
             }
-          });
-          std::vector<CsEnt>().swap(E);
+            std::sort(sec, sec + 64);
+            w[5] += (int64_t)(std::unique(sec, sec + 64) - sec);
+          }
+        }
+        for (int64_t q = 0; q < C; ++q) {
+          const int64_t o = ch * C + at(q, dtype == HSPMV_F32 ? 2 : 4);
+          const int64_t ov = ch * C + at(q, 2);
+          uint32_t ix = dummy << 16;  // padding: 0 * x[base] into the dummy slot
+          if (dtype == HSPMV_F32) {
+            uint32_t vb = 0;
+            if (q < ne) {
+              const CsEnt &e = src[q];
+              ix = (e.slot << 16) | (e.col - c0);
+              vb = value_f32(e.k, row_of(e.slot));
+            }
+            rec[(size_t)o] = ((uint64_t)vb << 32) | ix;
+          } else {
+            if (q < ne) {
+              const CsEnt &e = src[q];
+              ix = (e.slot << 16) | (e.col - c0);
+              val64[(size_t)ov] = value_f64(e.k, row_of(e.slot));
+            }
+            idx[(size_t)o] = ix;
+          }
         }
       });
-    for (auto &x : th) x.join();
-  }
+      std::vector<CsEnt>().swap(E);
+    }
+  });
   std::vector<uint32_t> mask;
   if (!lrow.empty()) {
     mask.assign((size_t)((m + 31) / 32), 0u);
@@ -554,11 +536,8 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   int rc;
   auto up = [&](auto **d, const auto &h) -> int {
     using E = typename std::decay_t<decltype(h)>::value_type;
-    const size_t bytes = sizeof(E) * std::max<size_t>(h.size(), 1);
-    int r2 = dev_alloc(d, bytes, &s.bytes);
-    if (r2) return r2;
-    if (!h.empty()) HIP_TRY(hipMemcpy(*d, h.data(), sizeof(E) * h.size(), hipMemcpyHostToDevice));
-    return HSPMV_OK;
+    if (h.empty()) return dev_alloc(d, sizeof(E), &s.bytes);  // one element's room, as for a size of 1
+    return upload(s, d, h.data(), sizeof(E) * h.size());
   };
   if ((rc = up(&s.d_cs_blk_c, blk_c)) || (rc = up(&s.d_cs_blk_r, wg_rows)) ||
       (rc = up(&s.d_cs_blk_v, blk_v)) || (rc = up(&s.d_cs_vslice, vslice)) || (rc = up(&s.d_cs_cbase, cbase)))

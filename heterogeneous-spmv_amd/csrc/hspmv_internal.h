@@ -1,8 +1,11 @@
-// Internal interfaces shared by the host runtime (hspmv_runtime.h units) and the
-// HIP kernels (spmv_kernels.hip).  Not part of the C ABI.
+// Internal interfaces shared by the host runtime (hspmv_runtime.h units), the
+// launch planner (hspmv_plan.cpp) and the HIP kernels (spmv_kernels.hip).  Not
+// part of the C ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
+
+#include "hspmv.h"
 
 namespace hspmv {
 
@@ -110,6 +113,45 @@ constexpr int32_t kSerialMax = 40;
 // r06s2), so fp64 keeps 40.
 constexpr int32_t kSerialMaxF32 = 56;
 constexpr int32_t kLongChunk = 4096;
+
+// ---- planner rules shared by plan_launch and the host tables: one
+// definition each, asked with the shape or the flags
+
+// Rows with more nonzeros than this are split rows (none: HSPMV_FLAG_NO_SPLIT).
+inline int32_t split_threshold(unsigned flags) {
+  return (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
+}
+
+// A matrix whose bytes stay under this is served from the 256 MiB Infinity
+// Cache across back-to-back SpMVs (the planner's "resident" test).
+constexpr double kMallResident = 192.0 * 1024 * 1024;
+// The bytes one SpMV touches: values + 32-bit columns, row pointers + y, x.
+inline double footprint_bytes(int64_t m, int64_t n, int64_t nnz, int dtype) {
+  const double sv = dtype == HSPMV_F64 ? 8.0 : 4.0;
+  return (double)nnz * (sv + 4.0) + (double)m * (sv + 4.0) + (double)n * sv;
+}
+inline bool mall_resident(int64_t m, int64_t n, int64_t nnz, int dtype) {
+  return footprint_bytes(m, n, nnz, dtype) <= kMallResident;
+}
+// The L2 of one XCD: gathers from an x (or a row group's slice of x) beyond
+// it miss L2.
+constexpr double kXcdL2Bytes = 4.0 * 1024 * 1024;
+
+// The fields of hspmv_options.flags (include/hspmv.h): the kernel code,
+// HSPMV_LANES(l), HSPMV_U(u) (5 bits below HSPMV_FLAG_PREFETCH),
+// HSPMV_XCD_CHUNK(s) (5 bits; 0 = automatic) and HSPMV_GROUPS(g) (3 bits; 1
+// when unset), the last two decoded from their log2 + 1 codes.
+inline unsigned flag_kernel(unsigned flags) { return flags & HSPMV_KERNEL_MASK; }
+inline int flag_lanes(unsigned flags) { return (int)((flags & HSPMV_LANES_MASK) >> HSPMV_LANES_SHIFT); }
+inline int flag_u(unsigned flags) { return (int)((flags >> HSPMV_U_SHIFT) & 0x1Fu); }
+inline int32_t flag_xcd_chunk(unsigned flags) {
+  const unsigned code = (flags >> HSPMV_XCD_CHUNK_SHIFT) & 0x1Fu;
+  return code ? 1 << (code - 1) : 0;
+}
+inline int32_t flag_groups(unsigned flags) {
+  const unsigned code = (flags >> HSPMV_GROUPS_SHIFT) & 0x7u;
+  return code ? 1 << (code - 1) : 1;
+}
 
 // Column-sorted row blocks (csort.hip): workgroup b works on column part
 // b % H (a fixed slice of x) and walks chunks [blk_c[b], blk_c[b+1]) of 64*u
@@ -248,7 +290,8 @@ inline int ssr_waves(double rows_per_ssr) {
   return w >= 6.0 ? 8 : (w >= 3.0 ? 4 : (w >= 1.5 ? 2 : 1));
 }
 
-// Chooses kernel / lanes / block shape for a shard (host-side heuristic).
+// Chooses kernel / lanes / block shape for a shard (host-side heuristic,
+// hspmv_plan.cpp).
 // rows_per_ssr: mean rows per super-super-row (CSR-3 workgroup-per-SSR plan);
 // packed_tasks > 0: CSR-3 tasks packed from super-rows (4 per workgroup).
 LaunchPlan plan_launch(const DevCSR &A, int dtype, unsigned flags, double rows_per_ssr,

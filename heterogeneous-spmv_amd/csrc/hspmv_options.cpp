@@ -118,7 +118,7 @@ void tuning_from_env(Tuning *) {}
 // still one add at a time in order), or with HSPMV_FLAG_NO_SPLIT stay in the
 // row kernels' lanes.
 int check_deterministic(unsigned flags, const Tuning &t) {
-  const unsigned k = flags & 0xFu;
+  const unsigned k = flag_kernel(flags);
   if ((t.deterministic == HSPMV_DETERMINISTIC_ORDERED || t.deterministic == HSPMV_DETERMINISTIC_SERIAL) &&
       k == kCsort)
     return set_error(HSPMV_E_INVALID, "the column-sorted kernel (HSPMV_KERNEL_CSORT) does not sum in "

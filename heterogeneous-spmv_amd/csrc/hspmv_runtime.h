@@ -1,11 +1,14 @@
 // hspmv_runtime.h -- the host runtime's internal state and the functions its
 // units share (not part of the C ABI).  The runtime is split by concern:
 //   hspmv_options.cpp      hspmv_options -> Tuning (+ diagnostic env knobs)
+//   hspmv_plan.cpp         plan_launch: the kernel and launch shape of a shard
+//                          (sees hspmv_internal.h only, not this header)
 //   hspmv_shard.cpp        device allocation, upload, launch-plan finish,
 //                          placement trials of one row-range shard
 //   hspmv_tables.cpp       host planner tables: 16-bit columns, wave tasks,
 //                          x windows, x slabs, split rows, CSR-3 SSR tasks
-//   hspmv_xdict.cpp        block x dictionaries (+ hspmv_xdict_plan)
+//   hspmv_xdict.cpp        block x dictionaries (+ hspmv_xdict_plan), the
+//                          plan entry points' shared preamble (plan_shape)
 //   hspmv_slices.cpp       row slices of dictionary handles (+ hspmv_slices_plan)
 //   hspmv_csort_build.cpp  column-sorted row blocks (csort.hip's tables)
 //   hspmv_multi.cpp        the row-range partition over devices, RCCL
@@ -20,7 +23,9 @@
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <thread>
 #include <vector>
 
 #include "hspmv_common.h"
@@ -138,9 +143,17 @@ struct hspmv_handle {
 
 namespace hspmv {
 
-// A matrix whose bytes stay under this is served from the 256 MiB Infinity
-// Cache across back-to-back SpMVs (the planner's "resident" test).
-constexpr double kMallResident = 192.0 * 1024 * 1024;
+// The host tables' thread pool: body(lo, hi, t) over [0, n) cut into nt equal
+// ranges, one thread each, nt = n / grain, at least 1 (which runs inline)
+// and at most 16.
+template <typename F>
+inline void parallel_ranges(int64_t n, int64_t grain, F &&body) {
+  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, n / grain));
+  if (nt == 1) return (void)body((int64_t)0, n, 0);
+  std::vector<std::thread> th;
+  for (int t = 0; t < nt; ++t) th.emplace_back([&, t]() { body(n * t / nt, n * (t + 1) / nt, t); });
+  for (auto &x : th) x.join();
+}
 
 // ---- hspmv_options.cpp
 int tuning_from_options(const hspmv_options *o, Tuning *t);
@@ -161,6 +174,13 @@ int dev_alloc_bytes(void **p, size_t bytes, int64_t *acc);
 template <typename T>
 inline int dev_alloc(T **p, size_t bytes, int64_t *acc) {
   return dev_alloc_bytes((void **)p, bytes, acc);
+}
+// dev_alloc into a slot of s (accounted in s.bytes) + the host-to-device copy
+// of the same bytes (none when bytes == 0).
+int upload_bytes(Shard &s, void **slot, const void *src, size_t bytes);
+template <typename T>
+inline int upload(Shard &s, T **slot, const void *src, size_t bytes) {
+  return upload_bytes(s, (void **)slot, src, bytes);
 }
 void free_shard(Shard &s, bool borrowed);
 int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_t r0, int64_t r1,
@@ -196,6 +216,16 @@ struct XdPlan {
   int32_t tmax = 0;
 };
 int xd_block_tasks(const Tuning &t, int task_waves);
+// What hspmv_xdict_plan_ex and hspmv_slices_plan plan for: the options as
+// Tuning + flags, the validated matrix's wave tasks (build_tasks), the tasks
+// per dictionary block W and the row kernel.
+struct PlanShape {
+  Tuning tune;
+  unsigned flags = 0;
+  std::vector<int32_t> tasks;
+  int W = 4, kern = kStream;
+};
+int plan_shape(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt, PlanShape &ps);
 int64_t xdict_cap_entries(int dtype, const Tuning &t);
 // slices: the workgroups' LDS is the dictionary alone (the slice kernel)
 bool plan_xdict_for(const int32_t *rp, const int32_t *col, int kern, int64_t m,

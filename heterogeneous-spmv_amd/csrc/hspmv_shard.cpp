@@ -35,6 +35,13 @@ int dev_alloc_bytes(void **p, size_t bytes, int64_t *acc) {
   return HSPMV_OK;
 }
 
+int upload_bytes(Shard &s, void **slot, const void *src, size_t bytes) {
+  const int rc = dev_alloc_bytes(slot, bytes, &s.bytes);
+  if (rc) return rc;
+  if (bytes) HIP_TRY(hipMemcpy(*slot, src, bytes, hipMemcpyHostToDevice));
+  return HSPMV_OK;
+}
+
 void free_shard(Shard &s, bool borrowed) {
   (void)hipSetDevice(s.device);
   if (!borrowed) {
@@ -90,23 +97,17 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
   HIP_TRY(hipSetDevice(s.device));
   s.row0 = r0;
   int rc;
-  if ((rc = dev_alloc(&s.d_rp, 4 * (size_t)(m + 1), &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_ci, 4 * (size_t)nnz, &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_val, sv * (size_t)nnz, &s.bytes))) return rc;
+  std::vector<int32_t> &rp = s.h_rp;
+  rp.resize((size_t)(m + 1));
+  for (int64_t i = 0; i <= m; ++i) rp[i] = (int32_t)(A->row_ptr[r0 + i] - k0);
+  if ((rc = upload(s, &s.d_rp, rp.data(), 4 * (size_t)(m + 1)))) return rc;
+  if ((rc = upload(s, &s.d_ci, A->col_idx + k0, 4 * (size_t)nnz))) return rc;
+  if ((rc = upload(s, &s.d_val, (const char *)A->val + sv * k0, sv * (size_t)nnz))) return rc;
   if ((rc = dev_alloc(&s.d_x, sv * (size_t)A->n, &s.bytes))) return rc;
   if (y_rows_alloc > 0) {
     if ((rc = dev_alloc(&s.d_y, sv * (size_t)y_rows_alloc, &s.bytes))) return rc;
   }
-  std::vector<int32_t> &rp = s.h_rp;
-  rp.resize((size_t)(m + 1));
-  for (int64_t i = 0; i <= m; ++i) rp[i] = (int32_t)(A->row_ptr[r0 + i] - k0);
-  HIP_TRY(hipMemcpy(s.d_rp, rp.data(), 4 * (size_t)(m + 1), hipMemcpyHostToDevice));
   s.x_entries = count_distinct_cols(A->col_idx + k0, nnz, A->n);
-  if (nnz) {
-    HIP_TRY(hipMemcpy(s.d_ci, A->col_idx + k0, 4 * (size_t)nnz, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s.d_val, (const char *)A->val + sv * k0, sv * (size_t)nnz,
-                      hipMemcpyHostToDevice));
-  }
   s.A.m = (int32_t)m;
   s.A.n = A->n;
   s.A.nnz = nnz;
@@ -123,10 +124,8 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
     in.resize((size_t)(nsr + 1));
     for (int64_t i = 0; i <= nssr; ++i) o[i] = (int32_t)(mp->outer[ssr0 + i] - sr0);
     for (int64_t i = 0; i <= nsr; ++i) in[i] = (int32_t)(mp->inner[sr0 + i] - r0);
-    if ((rc = dev_alloc(&s.d_outer, 4 * (size_t)(nssr + 1), &s.bytes))) return rc;
-    if ((rc = dev_alloc(&s.d_inner, 4 * (size_t)(nsr + 1), &s.bytes))) return rc;
-    HIP_TRY(hipMemcpy(s.d_outer, o.data(), 4 * (size_t)(nssr + 1), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s.d_inner, in.data(), 4 * (size_t)(nsr + 1), hipMemcpyHostToDevice));
+    if ((rc = upload(s, &s.d_outer, o.data(), 4 * o.size()))) return rc;
+    if ((rc = upload(s, &s.d_inner, in.data(), 4 * in.size()))) return rc;
     s.A.n_ssr = (int32_t)nssr;
     s.A.n_sr = (int32_t)nsr;
     s.A.outer = s.d_outer;
@@ -208,9 +207,7 @@ int place_shard(Shard &s, int64_t n, int dtype) {
   if (s.dp.sl_desc) return HSPMV_OK;  // row slices: the trial sets copy the CSR-order streams
   const size_t sv = dtype_size(dtype);
   const int64_t m = s.A.m, nnz = s.A.nnz;
-  if ((double)nnz * (double)(sv + 4) + (double)m * (double)(sv + 4) + (double)n * (double)sv <=
-      kMallResident)
-    return HSPMV_OK;  // served from the Infinity Cache: placement does not matter
+  if (mall_resident(m, n, nnz, dtype)) return HSPMV_OK;  // served from the Infinity Cache: placement does not matter
   struct Arr { void **slot; size_t bytes; };
   std::vector<Arr> arrs = {{(void **)&s.d_rp, 4 * (size_t)(m + 1)},
                            {(void **)&s.d_val, sv * (size_t)nnz},

@@ -5,7 +5,6 @@
 
 #include <algorithm>
 #include <cstddef>
-#include <thread>
 #include <vector>
 
 #include "hspmv_runtime.h"
@@ -73,15 +72,14 @@ int slices_why(const Tuning &t, unsigned flags, int kern, int W, const int32_t *
   if (kern == kCsr3) {
     if (t.csr3_plan == HSPMV_CSR3_PLAN_PACKED || t.csr3_plan == HSPMV_CSR3_PLAN_SSR || W != 4)
       return HSPMV_SLICES_SHAPE;
-  } else if (kern != kStream || ((flags >> 29) & 0x7u) > 1) {
+  } else if (kern != kStream || flag_groups(flags) > 1) {
     return HSPMV_SLICES_SHAPE;
   }
   if (c.max_rows > 64) return HSPMV_SLICES_SHAPE;
-  if (((flags >> 16) & 0x1Fu) || (flags & HSPMV_FLAG_PREFETCH) ||
+  if (flag_u(flags) || (flags & HSPMV_FLAG_PREFETCH) ||
       t.deterministic == HSPMV_DETERMINISTIC_SERIAL || t.serial_max > 0)
     return HSPMV_SLICES_CHUNKED;
-  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
-  if (c.max_len > long_t) return HSPMV_SLICES_SPLIT_ROWS;
+  if (c.max_len > split_threshold(flags)) return HSPMV_SLICES_SPLIT_ROWS;
   if (c.max_len > (dtype == HSPMV_F32 ? kSerialMaxF32 : kSerialMax)) return HSPMV_SLICES_LONG_ROW;
   const double sv = (double)dtype_size(dtype);
   const double nnz = (double)rp[m];
@@ -89,9 +87,7 @@ int slices_why(const Tuning &t, unsigned flags, int kern, int W, const int32_t *
       64.0 * (double)c.padded * (sv + 2.0) + (double)m + 8.0 * (double)(c.n_desc + 1) >
           nnz * (sv + 2.0) + 4.0 * (double)(m + 1))
     return HSPMV_SLICES_BYTES;
-  if (t.row_slices == 0 &&
-      nnz * (sv + 4.0) + (double)m * (sv + 4.0) + (double)n * sv <= kMallResident)
-    return HSPMV_SLICES_RESIDENT;
+  if (t.row_slices == 0 && mall_resident(m, n, rp[m], dtype)) return HSPMV_SLICES_RESIDENT;
   return HSPMV_SLICES_OK;
 }
 
@@ -124,35 +120,27 @@ void build_slices(const int32_t *rp, const uint16_t *pos, const void *val, int64
   for (int64_t r = 0; r < m; ++r) P.len[(size_t)r] = (uint8_t)(rp[r + 1] - rp[r]);
   P.pos.assign((size_t)std::max<int64_t>(64 * pre, 1), 0);
   P.val.assign(sv * (size_t)std::max<int64_t>(64 * pre, 1), 0);
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, nd / 256));
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t)
-    th.emplace_back([&, t]() {
-      for (int64_t s = nd * t / nt; s < nd * (t + 1) / nt; ++s) {
-        const int32_t a = starts[(size_t)s], b = starts[(size_t)s + 1];
-        const size_t base = 64 * (size_t)P.desc[2 * (size_t)s];
-        const int32_t w = P.desc[2 * (size_t)s + 2] - P.desc[2 * (size_t)s];
-        for (int32_t r = a; r < b; ++r)
-          for (int32_t k = 0; k < rp[r + 1] - rp[r]; ++k) {
-            const size_t src = (size_t)rp[r] + (size_t)k;
-            P.pos[slot_at(base, w, k, r - a, 4)] = pos[src];
-            memcpy(P.val.data() + sv * slot_at(base, w, k, r - a, G), (const char *)val + sv * src, sv);
-          }
-      }
-    });
-  for (auto &x : th) x.join();
+  parallel_ranges(nd, 256, [&](int64_t s0, int64_t s1, int) {
+    for (int64_t s = s0; s < s1; ++s) {
+      const int32_t a = starts[(size_t)s], b = starts[(size_t)s + 1];
+      const size_t base = 64 * (size_t)P.desc[2 * (size_t)s];
+      const int32_t w = P.desc[2 * (size_t)s + 2] - P.desc[2 * (size_t)s];
+      for (int32_t r = a; r < b; ++r)
+        for (int32_t k = 0; k < rp[r + 1] - rp[r]; ++k) {
+          const size_t src = (size_t)rp[r] + (size_t)k;
+          P.pos[slot_at(base, w, k, r - a, 4)] = pos[src];
+          memcpy(P.val.data() + sv * slot_at(base, w, k, r - a, G), (const char *)val + sv * src, sv);
+        }
+    }
+  });
 }
 
 int upload_slices(Shard &s, const SlicePlan &P) {
   int rc;
-  if ((rc = dev_alloc(&s.d_sl_desc, 4 * P.desc.size(), &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_sl_len, P.len.size(), &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_sl_pos, 2 * P.pos.size(), &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_sl_val, P.val.size(), &s.bytes))) return rc;
-  HIP_TRY(hipMemcpy(s.d_sl_desc, P.desc.data(), 4 * P.desc.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s.d_sl_len, P.len.data(), P.len.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s.d_sl_pos, P.pos.data(), 2 * P.pos.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s.d_sl_val, P.val.data(), P.val.size(), hipMemcpyHostToDevice));
+  if ((rc = upload(s, &s.d_sl_desc, P.desc.data(), 4 * P.desc.size()))) return rc;
+  if ((rc = upload(s, &s.d_sl_len, P.len.data(), P.len.size()))) return rc;
+  if ((rc = upload(s, &s.d_sl_pos, P.pos.data(), 2 * P.pos.size()))) return rc;
+  if ((rc = upload(s, &s.d_sl_val, P.val.data(), P.val.size()))) return rc;
   s.sl_bytes = (int64_t)(4 * P.desc.size() + P.len.size() + 2 * P.pos.size() + P.val.size());
   s.sl_desc_n = (int64_t)P.desc.size() / 2 - 1;
   s.sl_padded = P.padded;
@@ -185,23 +173,12 @@ int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hsp
   *n_desc = *n_slices = *padded_entries = 0;
   *why = HSPMV_SLICES_SHAPE;
   int rc;
-  Tuning tune;
-  if ((rc = tuning_from_options(opt, &tune))) return rc;
-  const unsigned flags = opt ? opt->flags : 0u;
-  if ((rc = validate_host_csr(A, true))) return rc;
-  if ((rc = validate_host_maps(maps, A->m))) return rc;
-  std::vector<int32_t> tasks;
-  const bool csr3 = maps && maps->n_ssr > 0;
-  int waves = 4;
-  if (csr3) {
-    const std::vector<int32_t> inner(maps->inner, maps->inner + maps->n_sr + 1);
-    const std::vector<int32_t> outer(maps->outer, maps->outer + maps->n_ssr + 1);
-    build_tasks(A->row_ptr, A->m, &inner, &outer, flags, tune, tasks, &waves);
-  } else {
-    build_tasks(A->row_ptr, A->m, nullptr, nullptr, flags, tune, tasks, &waves);
-  }
-  const int W = xd_block_tasks(tune, waves);
-  const int kern = kernel_for_tables(csr3 ? maps->n_ssr : 0, !tasks.empty(), flags);
+  PlanShape ps;
+  if ((rc = plan_shape(A, maps, opt, ps))) return rc;
+  const Tuning &tune = ps.tune;
+  const unsigned flags = ps.flags;
+  std::vector<int32_t> &tasks = ps.tasks;
+  const int W = ps.W, kern = ps.kern;
   if ((kern != kStream && kern != kCsr3) || A->m == 0) return HSPMV_OK;
   SliceCounts c;
   *why = slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, A->dtype,
@@ -211,7 +188,7 @@ int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hsp
   *padded_entries = 64 * c.padded;
   if (*why != HSPMV_SLICES_OK) return HSPMV_OK;
   XdPlan P;
-  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
+  const int32_t long_t = split_threshold(flags);
   const bool fill = desc || len || pos || val;
   int64_t cut = 0;
   if (!plan_xdict_for(A->row_ptr, A->col_idx, kern, A->m, tasks, W, long_t,

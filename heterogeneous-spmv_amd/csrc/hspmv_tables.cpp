@@ -7,7 +7,6 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
-#include <thread>
 #include <vector>
 
 #include "hspmv_runtime.h"
@@ -39,20 +38,12 @@ int build_col16(Shard &s, const int32_t *col, int64_t nnz, int64_t m, int64_t n,
   *used = false;
   if (nnz == 0) return HSPMV_OK;
   const bool forced = (flags & HSPMV_FLAG_COL16) != 0 && !(flags & HSPMV_FLAG_NO_COL16);
-  const double sv = (double)dtype_size(dtype);
-  if (!forced && (double)nnz * (sv + 4.0) + (double)m * (sv + 4.0) + (double)n * sv <= kMallResident)
-    return HSPMV_OK;
+  if (!forced && mall_resident(m, n, nnz, dtype)) return HSPMV_OK;
   const int64_t B = int64_t(1) << kC16Shift;
   const int64_t nb = (nnz + B - 1) / B;
   std::vector<int32_t> base((size_t)nb + 1, 0);  // +1: kernels load bases in pairs
   std::vector<int32_t> span((size_t)nb, 0);
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, nb / 4096));
-  auto par = [&](auto &&body) {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back([&, t]() { body(nb * t / nt, nb * (t + 1) / nt); });
-    for (auto &x : th) x.join();
-  };
-  par([&](int64_t b0, int64_t b1) {
+  parallel_ranges(nb, 4096, [&](int64_t b0, int64_t b1, int) {
     for (int64_t b = b0; b < b1; ++b) {
       const int64_t k0 = b * B, k1 = std::min(nnz, k0 + B);
       int32_t lo = col[k0], hi = col[k0];
@@ -75,7 +66,7 @@ int build_col16(Shard &s, const int32_t *col, int64_t nnz, int64_t m, int64_t n,
   const int64_t nw = (nnz + 63) / 64 + 1;  // +1: kernels load words in pairs
   std::vector<uint16_t> off((size_t)nnz);
   std::vector<uint64_t> pl((size_t)(planes * nw), 0);
-  par([&](int64_t b0, int64_t b1) {
+  parallel_ranges(nb, 4096, [&](int64_t b0, int64_t b1, int) {
     // blocks are 4 words wide, so threads never share a plane word
     for (int64_t b = b0; b < b1; ++b) {
       const int64_t k0 = b * B, k1 = std::min(nnz, k0 + B);
@@ -88,14 +79,9 @@ int build_col16(Shard &s, const int32_t *col, int64_t nnz, int64_t m, int64_t n,
     }
   });
   int rc;
-  if ((rc = dev_alloc(&s.d_c16, 2 * (size_t)nnz, &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_cbase, 4 * (size_t)(nb + 1), &s.bytes))) return rc;
-  HIP_TRY(hipMemcpy(s.d_c16, off.data(), 2 * (size_t)nnz, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s.d_cbase, base.data(), 4 * (size_t)(nb + 1), hipMemcpyHostToDevice));
-  if (planes) {
-    if ((rc = dev_alloc(&s.d_cplanes, 8 * pl.size(), &s.bytes))) return rc;
-    HIP_TRY(hipMemcpy(s.d_cplanes, pl.data(), 8 * pl.size(), hipMemcpyHostToDevice));
-  }
+  if ((rc = upload(s, &s.d_c16, off.data(), 2 * off.size()))) return rc;
+  if ((rc = upload(s, &s.d_cbase, base.data(), 4 * base.size()))) return rc;
+  if (planes && (rc = upload(s, &s.d_cplanes, pl.data(), 8 * pl.size()))) return rc;
   s.A.col16 = s.d_c16;
   s.A.cbase = s.d_cbase;
   s.A.cplanes = s.d_cplanes;
@@ -123,11 +109,9 @@ int build_col16g(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int
   const int mode = s.tune.col16_group;  // -1 off, 0 auto, 1 on whenever it fits
   const int64_t nnz = rp[m];
   if (mode < 0 || (flags & HSPMV_FLAG_NO_COL16) || nnz == 0) return HSPMV_OK;
-  const double sv = (double)dtype_size(dtype);
   const bool forced = (flags & HSPMV_FLAG_COL16) != 0 || mode == 1;
-  if (!forced && (double)nnz * (sv + 4.0) + (double)m * (sv + 4.0) + (double)n * sv > kMallResident)
-    return HSPMV_OK;
-  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
+  if (!forced && !mall_resident(m, n, nnz, dtype)) return HSPMV_OK;
+  const int32_t long_t = split_threshold(flags);
   const int64_t ng = starts ? (int64_t)starts->size() - 1 : (m + 63) / 64;
   if (ng <= 0) return HSPMV_OK;
   auto rows = [&](int64_t g, int64_t &r0, int64_t &r1) {
@@ -136,13 +120,7 @@ int build_col16g(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int
   };
   std::vector<int32_t> base((size_t)ng + 1, 0);  // +1: read by 8-byte scalar loads
   std::vector<int32_t> span((size_t)ng, 0);
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, ng / 4096));
-  auto par = [&](auto &&body) {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back([&, t]() { body(ng * t / nt, ng * (t + 1) / nt); });
-    for (auto &x : th) x.join();
-  };
-  par([&](int64_t g0, int64_t g1) {
+  parallel_ranges(ng, 4096, [&](int64_t g0, int64_t g1, int) {
     for (int64_t g = g0; g < g1; ++g) {
       int32_t lo = INT32_MAX, hi = -1;
       int64_t ra, rb;
@@ -162,7 +140,7 @@ int build_col16g(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int
   for (int32_t v : span) maxspan = std::max(maxspan, v);
   if (maxspan > 65535) return HSPMV_OK;
   std::vector<uint16_t> off((size_t)nnz, 0);
-  par([&](int64_t g0, int64_t g1) {
+  parallel_ranges(ng, 4096, [&](int64_t g0, int64_t g1, int) {
     for (int64_t g = g0; g < g1; ++g) {
       int64_t ra, rb;
       rows(g, ra, rb);
@@ -173,10 +151,8 @@ int build_col16g(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int
     }
   });
   int rc;
-  if ((rc = dev_alloc(&s.d_c16, 2 * (size_t)nnz, &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_cbase, 4 * base.size(), &s.bytes))) return rc;
-  HIP_TRY(hipMemcpy(s.d_c16, off.data(), 2 * (size_t)nnz, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s.d_cbase, base.data(), 4 * base.size(), hipMemcpyHostToDevice));
+  if ((rc = upload(s, &s.d_c16, off.data(), 2 * off.size()))) return rc;
+  if ((rc = upload(s, &s.d_cbase, base.data(), 4 * base.size()))) return rc;
   int bits = 0;
   while (bits < 31 && (int64_t(1) << bits) <= maxspan) ++bits;
   s.A.col_span_bits = std::max(1, bits);
@@ -372,6 +348,26 @@ void cap_task_nnz(const int32_t *rp, int32_t long_t, int32_t budget, std::vector
   ts.swap(out);
 }
 
+// Nonzeros in heavy 64-row groups (those whose in-kernel rows, up to long_t
+// nonzeros each, hold more than `budget`), and in all groups.
+struct HeavyGroups {
+  int64_t heavy = 0, total = 0;
+};
+
+HeavyGroups heavy_groups(const int32_t *rp, int64_t m, int32_t long_t, int32_t budget) {
+  HeavyGroups h;
+  for (int64_t g = 0; g < m; g += 64) {
+    int64_t in = 0;
+    for (int64_t r = g; r < std::min(m, g + 64); ++r) {
+      const int64_t len = rp[r + 1] - rp[r];
+      in += len > long_t ? 0 : len;
+    }
+    h.total += in;
+    h.heavy += in > budget ? in : 0;
+  }
+  return h;
+}
+
 // The wave tasks of a shard (empty: STREAM's fixed 64-row groups) and the
 // tasks per workgroup (*waves).  CSR-3: 64-row aligned groups or packed
 // super-rows, 4 per workgroup; or the SSR plan's W per super-super-row.
@@ -397,7 +393,7 @@ void build_tasks(const int32_t *rp, int64_t m, const std::vector<int32_t> *inner
       ssr_tasks(rp, m, *outer, *inner, *waves, ts);
     return;
   }
-  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
+  const int32_t long_t = split_threshold(flags);
   const int32_t budget = task_nnz_budget(tune);
   if (inner && csr3_fill(tune)) {
     for (int64_t g = 0; g < m; g += 64) ts.push_back((int32_t)g);
@@ -406,19 +402,10 @@ void build_tasks(const int32_t *rp, int64_t m, const std::vector<int32_t> *inner
   } else if (inner) {
     pack_csr3_tasks(*inner, (int32_t)m, ts);
   } else {
-    const unsigned k = flags & 0xFu;
+    const unsigned k = flag_kernel(flags);
     if ((k != kAuto && k != kCsr3) || m == 0) return;
-    int64_t heavy = 0, total = 0;
-    for (int64_t g = 0; g < m; g += 64) {
-      int64_t in = 0;
-      for (int64_t r = g; r < std::min(m, g + 64); ++r) {
-        const int64_t len = rp[r + 1] - rp[r];
-        in += len > long_t ? 0 : len;
-      }
-      total += in;
-      heavy += in > budget ? in : 0;
-    }
-    if (4 * heavy < total || heavy == 0) return;
+    const HeavyGroups h = heavy_groups(rp, m, long_t, budget);
+    if (4 * h.heavy < h.total || h.heavy == 0) return;
     for (int64_t g = 0; g < m; g += 64) ts.push_back((int32_t)g);
     ts.push_back((int32_t)m);
   }
@@ -440,29 +427,25 @@ std::vector<int32_t> xwin_table(const int32_t *rp, const int32_t *col, int64_t m
   const int64_t ng = starts ? (int64_t)starts->size() - 1 : (m + 63) / 64;
   if (ng <= 0) return tab;
   tab.assign((size_t)(2 * ng), 0);
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, ng / 4096));
-  std::vector<int64_t> fit((size_t)nt, 0);
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t)
-    th.emplace_back([&, t]() {
-      for (int64_t g = ng * t / nt; g < ng * (t + 1) / nt; ++g) {
-        const int64_t r0 = starts ? (*starts)[(size_t)g] : 64 * g;
-        const int64_t r1 = starts ? (*starts)[(size_t)g + 1] : std::min(m, 64 * g + 64);
-        const int64_t k0 = rp[r0], k1 = rp[r1];
-        if (k1 <= k0) continue;
-        int32_t lo = col[k0], hi = col[k0];
-        for (int64_t k = k0 + 1; k < k1; ++k) {
-          lo = std::min(lo, col[k]);
-          hi = std::max(hi, col[k]);
-        }
-        if ((int64_t)hi - lo + 1 <= kXWin) {
-          tab[(size_t)(2 * g)] = lo;
-          tab[(size_t)(2 * g + 1)] = hi - lo + 1;
-          ++fit[(size_t)t];
-        }
+  int64_t fit[16] = {0};  // per thread of parallel_ranges
+  parallel_ranges(ng, 4096, [&](int64_t g0, int64_t g1, int t) {
+    for (int64_t g = g0; g < g1; ++g) {
+      const int64_t r0 = starts ? (*starts)[(size_t)g] : 64 * g;
+      const int64_t r1 = starts ? (*starts)[(size_t)g + 1] : std::min(m, 64 * g + 64);
+      const int64_t k0 = rp[r0], k1 = rp[r1];
+      if (k1 <= k0) continue;
+      int32_t lo = col[k0], hi = col[k0];
+      for (int64_t k = k0 + 1; k < k1; ++k) {
+        lo = std::min(lo, col[k]);
+        hi = std::max(hi, col[k]);
       }
-    });
-  for (auto &x : th) x.join();
+      if ((int64_t)hi - lo + 1 <= kXWin) {
+        tab[(size_t)(2 * g)] = lo;
+        tab[(size_t)(2 * g + 1)] = hi - lo + 1;
+        ++fit[t];
+      }
+    }
+  });
   int64_t nfit = 0;
   for (int64_t f : fit) nfit += f;
   if (2 * nfit < ng) tab.clear();
@@ -540,24 +523,17 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
                  int64_t n, int dtype, unsigned flags) {
   s.n_slabs = 0;
   const int forced = s.tune.x_slabs < 0 ? 0 : (s.tune.x_slabs > 0 ? s.tune.x_slabs : -1);  // -1 auto, 0 off, B slabs
-  if (forced == 0 || !val || m == 0 || n == 0 || (flags & 0xFu) == kVector) return HSPMV_OK;
+  if (forced == 0 || !val || m == 0 || n == 0 || flag_kernel(flags) == kVector) return HSPMV_OK;
   const int64_t nnz = rp[m];
   const double sv = (double)dtype_size(dtype);
   const double slab_bytes = s.tune.xslab_bytes > 0 ? std::max(4096.0, s.tune.xslab_bytes) : kSlabBytes;
   int B = forced > 0 ? forced : (int)std::ceil((double)n * sv / slab_bytes);
   B = (int)std::min<int64_t>(std::min(B, kMaxSlabs), n);
   if (B < 2) return HSPMV_OK;
-  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
+  const int32_t long_t = split_threshold(flags);
   const int64_t W = (n + B - 1) / B;  // columns per slab
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, m / 65536));
-  auto par = [&](auto &&body) {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back([&, t]() { body(t); });
-    for (auto &x : th) x.join();
-  };
   if (forced < 0) {
-    const double footprint = (double)nnz * (sv + 4.0) + (double)m * (sv + 4.0) + (double)n * sv;
-    if (footprint <= kMallResident || (double)n * sv <= 4.0 * 1024 * 1024) return HSPMV_OK;
+    if (mall_resident(m, n, nnz, dtype) || (double)n * sv <= kXcdL2Bytes) return HSPMV_OK;
     // the passes must pay: every extra one re-reads a row-pointer array and
     // y and rewrites y (at most a quarter of the matrix stream in total),
     // and each pass must stream millions of nonzeros (a launch is ~2-5 us)
@@ -570,13 +546,13 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
     // without slabs, and the extra passes only cost (deterministic handles
     // on mix: 284 us with four slabs vs 209 without; profiles/r04/
     // sweep_deterministic.jsonl)
-    if (median_group_span(rp, col, m) * sv <= 4.0 * 1024 * 1024) return HSPMV_OK;
+    if (median_group_span(rp, col, m) * sv <= kXcdL2Bytes) return HSPMV_OK;
   }
   // per (slab, row) segment lengths; rows must be slab-monotone
   std::vector<int32_t> srp((size_t)B * (size_t)(m + 1), 0);
   std::atomic<bool> unsorted{false};
-  par([&](int t) {
-    for (int64_t r = m * t / nt; r < m * (t + 1) / nt; ++r) {
+  parallel_ranges(m, 65536, [&](int64_t ra, int64_t rb, int) {
+    for (int64_t r = ra; r < rb; ++r) {
       const int32_t k0 = rp[r], k1 = rp[r + 1];
       if (k1 - k0 > long_t) continue;  // split rows: empty segments
       int64_t prev = 0;
@@ -599,8 +575,8 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
   const int64_t snnz = base;  // in-kernel nonzeros (split rows excluded)
   std::vector<int32_t> scol((size_t)std::max<int64_t>(snnz, 1));
   std::vector<char> sval((size_t)std::max<int64_t>(snnz, 1) * (size_t)sv);
-  par([&](int t) {
-    for (int64_t r = m * t / nt; r < m * (t + 1) / nt; ++r) {
+  parallel_ranges(m, 65536, [&](int64_t ra, int64_t rb, int) {
+    for (int64_t r = ra; r < rb; ++r) {
       const int32_t k0 = rp[r], k1 = rp[r + 1];
       if (k1 - k0 > long_t) continue;
       int32_t k = k0;
@@ -615,12 +591,9 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
     }
   });
   int rc;
-  if ((rc = dev_alloc(&s.d_slab_rp, 4 * srp.size(), &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_slab_col, 4 * scol.size(), &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_slab_val, sval.size(), &s.bytes))) return rc;
-  HIP_TRY(hipMemcpy(s.d_slab_rp, srp.data(), 4 * srp.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s.d_slab_col, scol.data(), 4 * scol.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s.d_slab_val, sval.data(), sval.size(), hipMemcpyHostToDevice));
+  if ((rc = upload(s, &s.d_slab_rp, srp.data(), 4 * srp.size()))) return rc;
+  if ((rc = upload(s, &s.d_slab_col, scol.data(), 4 * scol.size()))) return rc;
+  if ((rc = upload(s, &s.d_slab_val, sval.data(), sval.size()))) return rc;
   s.n_slabs = B;
   return HSPMV_OK;
 }
@@ -640,18 +613,8 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
 constexpr double kSlabHeavyShare = 0.125;
 
 void slab_kernel_rule(Shard &s, const int32_t *rp, int64_t m, unsigned flags) {
-  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
-  int64_t heavy = 0, total = 0;
-  for (int64_t g = 0; g < m; g += 64) {
-    int64_t in = 0;
-    for (int64_t r = g; r < std::min(m, g + 64); ++r) {
-      const int64_t len = rp[r + 1] - rp[r];
-      in += len > long_t ? 0 : len;
-    }
-    total += in;
-    heavy += in > task_nnz_budget(s.tune) ? in : 0;
-  }
-  s.heavy_frac = total ? (double)heavy / (double)total : 0.0;
+  const HeavyGroups h = heavy_groups(rp, m, split_threshold(flags), task_nnz_budget(s.tune));
+  s.heavy_frac = h.total ? (double)h.heavy / (double)h.total : 0.0;
   s.A.slab_stream = s.heavy_frac < kSlabHeavyShare;
 }
 
@@ -685,10 +648,9 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
   s.h_xwin_t.clear();
   int rc;
   {
-    const unsigned kf = flags & 0xFu;
+    const unsigned kf = flag_kernel(flags);
     const int cm = s.tune.csort;  // -1 off, 0 auto, 1 whenever it can be built
     const double sv = (double)dtype_size(dtype);
-    const double footprint = (double)rp[m] * (sv + 4.0) + (double)m * (sv + 4.0) + (double)n * sv;
     // an ordered or serial handle (deterministic = 1, 3) never builds the
     // csort tables: the planner would pick kCsort whenever they exist
     // (plan_launch); a reproducible one (2) builds them with fixed-point slots
@@ -701,7 +663,7 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
     // at 90.8 us against csort's 62.5 (profiles/r04/auto_regret_f32.jsonl);
     // x of a few L1s (the zoo's `tall`, 16-32 KiB) stays on the row kernels.
     if (!want && kf == kAuto && cm == 0 && !ordered && s.tune.x_slabs == 0 &&
-        footprint > kMallResident && (double)n * sv > 256.0 * 1024)
+        !mall_resident(m, n, rp[m], dtype) && (double)n * sv > 256.0 * 1024)
       want = irregular_gathers(rp, col, m, sv);
     if (want) {
       if ((rc = build_csort(s, rp, col, val, m, n, dtype, flags))) return rc;
@@ -781,9 +743,8 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags) {
     if (!lrow.empty() && s.dp.serial_max == INT32_MAX) {  // serial order: one workgroup per row
       int rc;
       const int64_t nl = (int64_t)lrow.size();
-      if ((rc = dev_alloc(&s.d_long_row, 4 * (size_t)nl, &s.bytes))) return rc;
+      if ((rc = upload(s, &s.d_long_row, lrow.data(), 4 * lrow.size()))) return rc;
       if ((rc = dev_alloc(&s.d_partials, dtype_size(dtype) * (size_t)nl, &s.bytes))) return rc;
-      HIP_TRY(hipMemcpy(s.d_long_row, lrow.data(), 4 * (size_t)nl, hipMemcpyHostToDevice));
       s.dp.partials = s.d_partials;  // the rows' sums, scattered into y after the row kernel
       s.dp.long_t = kLongRow;
       s.dp.n_long = (int32_t)nl;
@@ -798,13 +759,10 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags) {
     } else if (!lrow.empty()) {
       int rc;
       const int64_t nl = (int64_t)lrow.size(), nc = (int64_t)ck.size() / 2;
-      if ((rc = dev_alloc(&s.d_long_row, 4 * (size_t)nl, &s.bytes))) return rc;
-      if ((rc = dev_alloc(&s.d_long_cstart, 4 * (size_t)(nl + 1), &s.bytes))) return rc;
-      if ((rc = dev_alloc(&s.d_chunk_k, 8 * (size_t)nc, &s.bytes))) return rc;
+      if ((rc = upload(s, &s.d_long_row, lrow.data(), 4 * lrow.size()))) return rc;
+      if ((rc = upload(s, &s.d_long_cstart, lcs.data(), 4 * lcs.size()))) return rc;
+      if ((rc = upload(s, &s.d_chunk_k, ck.data(), 4 * ck.size()))) return rc;
       if ((rc = dev_alloc(&s.d_partials, dtype_size(dtype) * (size_t)nc, &s.bytes))) return rc;
-      HIP_TRY(hipMemcpy(s.d_long_row, lrow.data(), 4 * (size_t)nl, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(s.d_long_cstart, lcs.data(), 4 * (size_t)(nl + 1), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(s.d_chunk_k, ck.data(), 8 * (size_t)nc, hipMemcpyHostToDevice));
       s.dp.long_t = kLongRow;
       s.dp.n_long = (int32_t)nl;
       s.dp.n_chunks = (int32_t)nc;
@@ -886,16 +844,14 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags) {
   const std::vector<int32_t> &xw = s.plan.kernel == kStream ? s.h_xwin : s.h_xwin_t;
   if ((s.plan.kernel == kStream || (s.plan.kernel == kCsr3 && !s.h_tasks.empty())) && !xw.empty()) {
     int rc;
-    if ((rc = dev_alloc(&s.d_xwin, 4 * xw.size(), &s.bytes))) return rc;
-    HIP_TRY(hipMemcpy(s.d_xwin, xw.data(), 4 * xw.size(), hipMemcpyHostToDevice));
+    if ((rc = upload(s, &s.d_xwin, xw.data(), 4 * xw.size()))) return rc;
     s.dp.xwin = s.d_xwin;
   }
   std::vector<int32_t>().swap(s.h_xwin);
   std::vector<int32_t>().swap(s.h_xwin_t);
   if (s.plan.kernel == kCsr3 && !s.h_tasks.empty()) {
     int rc;
-    if ((rc = dev_alloc(&s.d_task, 4 * s.h_tasks.size(), &s.bytes))) return rc;
-    HIP_TRY(hipMemcpy(s.d_task, s.h_tasks.data(), 4 * s.h_tasks.size(), hipMemcpyHostToDevice));
+    if ((rc = upload(s, &s.d_task, s.h_tasks.data(), 4 * s.h_tasks.size()))) return rc;
     s.dp.task_start = s.d_task;
     s.dp.n_tasks = (int32_t)(s.h_tasks.size() - 1);
     s.dp.task_align = ssr_aligned(s.tune) ? 1 : 0;

@@ -7,7 +7,6 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
-#include <thread>
 #include <vector>
 
 #include "hspmv_runtime.h"
@@ -35,7 +34,7 @@ constexpr int32_t kXdCapBytes = 20 * 1024;  // + 8-12 KB of product staging: 6 b
 // Which row kernel the planner will pick (plan_launch) for a shard with
 // n_ssr super-super-rows and (CSR-3) packed tasks.
 int kernel_for_tables(int64_t n_ssr, bool have_tasks, unsigned flags) {
-  const unsigned k = flags & 0xFu;
+  const unsigned k = flag_kernel(flags);
   if (k == kVector) return kVector;
   if ((k == kCsr3 || k == kAuto) && n_ssr > 0)
     return have_tasks ? kCsr3 : -1;
@@ -50,14 +49,8 @@ bool plan_xdict(const int32_t *rp, const int32_t *col, const std::vector<int32_t
   const int64_t nnz = rp[bs.back()];
   std::vector<std::vector<int32_t>> runs((size_t)nb);  // per block: start, end (inclusive) pairs
   std::vector<int32_t> total((size_t)nb, 0);
-  const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, nb / 256));
   std::atomic<bool> fail{false};
-  auto par = [&](auto &&body) {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back([&, t]() { body(nb * t / nt, nb * (t + 1) / nt); });
-    for (auto &x : th) x.join();
-  };
-  par([&](int64_t b0, int64_t b1) {
+  parallel_ranges(nb, 256, [&](int64_t b0, int64_t b1, int) {
     std::vector<int32_t> c;
     for (int64_t b = b0; b < b1 && !fail.load(std::memory_order_relaxed); ++b) {
       c.clear();
@@ -102,8 +95,8 @@ bool plan_xdict(const int32_t *rp, const int32_t *col, const std::vector<int32_t
     if (rp[r + 1] - rp[r] <= long_t) P.in_kernel_nnz += rp[r + 1] - rp[r];
   if (!fill) return true;
   P.rec.assign((size_t)(2 * nrec), 0);
-  P.pos.assign((size_t)nnz, 0);
-  par([&](int64_t b0, int64_t b1) {
+  P.pos.assign((size_t)std::max<int64_t>(nnz, 1), 0);  // (never empty: uploaded as it stands)
+  parallel_ranges(nb, 256, [&](int64_t b0, int64_t b1, int) {
     for (int64_t b = b0; b < b1; ++b) {
       const std::vector<int32_t> &R = runs[(size_t)b];
       const int64_t nr = (int64_t)R.size() / 2;
@@ -255,12 +248,11 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   if (kern != kStream && kern != kCsr3) return HSPMV_OK;
   const int W = xd_block_tasks(s.tune, s.A.task_waves);
   if (kern == kCsr3 && W != 4 && W != 8) return HSPMV_OK;  // the XD kernels run 4 or 8 waves
-  if (kern == kStream && ((flags >> 29) & 0x7u) > 1) return HSPMV_OK;  // groups != 1
+  if (kern == kStream && flag_groups(flags) > 1) return HSPMV_OK;  // groups != 1
   const double sv = (double)dtype_size(dtype);
   const int64_t nnz = rp[m];
-  const double footprint = (double)nnz * (sv + 4.0) + (double)m * (sv + 4.0) + (double)n * sv;
-  if (mode < 0 && footprint <= kMallResident) return HSPMV_OK;
-  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
+  if (mode < 0 && mall_resident(m, n, nnz, dtype)) return HSPMV_OK;
+  const int32_t long_t = split_threshold(flags);
   XdPlan P;
   // (cuts the task table only when the dictionaries are taken)
   std::vector<int32_t> tasks = s.h_tasks;
@@ -283,14 +275,11 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
     build_slices(rp, P.pos.data(), val, m, dtype, slice_starts(kern, m, s.h_tasks), S);
     if ((rc = upload_slices(s, S))) return rc;
     s.A.has_slices = true;
-  } else {
-    if ((rc = dev_alloc(&s.d_c16, 2 * (size_t)std::max<int64_t>(nnz, 1), &s.bytes))) return rc;
-    if (nnz) HIP_TRY(hipMemcpy(s.d_c16, P.pos.data(), 2 * (size_t)nnz, hipMemcpyHostToDevice));
+  } else if ((rc = upload(s, &s.d_c16, P.pos.data(), 2 * P.pos.size()))) {
+    return rc;
   }
-  if ((rc = dev_alloc(&s.d_xd_blk, 4 * P.blk.size(), &s.bytes))) return rc;
-  if ((rc = dev_alloc(&s.d_xd_runs, 4 * P.rec.size(), &s.bytes))) return rc;
-  HIP_TRY(hipMemcpy(s.d_xd_blk, P.blk.data(), 4 * P.blk.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(s.d_xd_runs, P.rec.data(), 4 * P.rec.size(), hipMemcpyHostToDevice));
+  if ((rc = upload(s, &s.d_xd_blk, P.blk.data(), 4 * P.blk.size()))) return rc;
+  if ((rc = upload(s, &s.d_xd_runs, P.rec.data(), 4 * P.rec.size()))) return rc;
   s.A.col16 = slices ? s.d_sl_pos : s.d_c16;  // the 16-bit position stream the launch reads
   s.A.cbase = nullptr;
   s.A.cplanes = nullptr;
@@ -300,6 +289,30 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   s.xd_lds_bytes = (int32_t)((int64_t)P.tmax * (int64_t)sv);
   s.xd_entries = P.entries;
   s.xd_runs_n = (int64_t)P.rec.size() / 2;
+  return HSPMV_OK;
+}
+
+// The shared opening of hspmv_xdict_plan_ex and hspmv_slices_plan: the
+// options, the validated matrix and maps, and the tasks / block shape / row
+// kernel the host tables of a handle are built for (build_row_tables,
+// build_xdict: the same build_tasks, xd_block_tasks and kernel_for_tables).
+int plan_shape(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt, PlanShape &ps) {
+  int rc;
+  if ((rc = tuning_from_options(opt, &ps.tune))) return rc;
+  ps.flags = opt ? opt->flags : 0u;
+  if ((rc = validate_host_csr(A, true))) return rc;
+  if ((rc = validate_host_maps(maps, A->m))) return rc;
+  const bool csr3 = maps && maps->n_ssr > 0;
+  int waves = 4;
+  if (csr3) {
+    const std::vector<int32_t> inner(maps->inner, maps->inner + maps->n_sr + 1);
+    const std::vector<int32_t> outer(maps->outer, maps->outer + maps->n_ssr + 1);
+    build_tasks(A->row_ptr, A->m, &inner, &outer, ps.flags, ps.tune, ps.tasks, &waves);
+  } else {
+    build_tasks(A->row_ptr, A->m, nullptr, nullptr, ps.flags, ps.tune, ps.tasks, &waves);
+  }
+  ps.W = xd_block_tasks(ps.tune, waves);
+  ps.kern = kernel_for_tables(csr3 ? maps->n_ssr : 0, !ps.tasks.empty(), ps.flags);
   return HSPMV_OK;
 }
 
@@ -317,28 +330,17 @@ int hspmv_xdict_plan_ex(const hspmv_csr *A, const hspmv_csr3_maps *maps, const h
   *n_blocks = 0;
   *n_records = 0;
   int rc;
-  Tuning tune;
-  if ((rc = tuning_from_options(opt, &tune))) return rc;
-  const unsigned flags = opt ? opt->flags : 0u;
-  if ((rc = validate_host_csr(A, true))) return rc;
-  if ((rc = validate_host_maps(maps, A->m))) return rc;
-  std::vector<int32_t> tasks;
-  const bool csr3 = maps && maps->n_ssr > 0;
-  int waves = 4;
-  if (csr3) {
-    const std::vector<int32_t> inner(maps->inner, maps->inner + maps->n_sr + 1);
-    const std::vector<int32_t> outer(maps->outer, maps->outer + maps->n_ssr + 1);
-    build_tasks(A->row_ptr, A->m, &inner, &outer, flags, tune, tasks, &waves);
-  } else {
-    build_tasks(A->row_ptr, A->m, nullptr, nullptr, flags, tune, tasks, &waves);
-  }
-  const int W = xd_block_tasks(tune, waves);
-  const int kern = kernel_for_tables(csr3 ? maps->n_ssr : 0, !tasks.empty(), flags);
+  PlanShape ps;
+  if ((rc = plan_shape(A, maps, opt, ps))) return rc;
+  const Tuning &tune = ps.tune;
+  const unsigned flags = ps.flags;
+  std::vector<int32_t> &tasks = ps.tasks;
+  const int W = ps.W, kern = ps.kern;
   if ((kern != kStream && kern != kCsr3) || A->m == 0 || (kern == kCsr3 && W != 4 && W != 8))
     return HSPMV_OK;
   if (cap_entries <= 0) cap_entries = xdict_cap_entries(A->dtype, tune);
   XdPlan P;
-  const int32_t long_t = (flags & HSPMV_FLAG_NO_SPLIT) ? INT32_MAX : kLongRow;
+  const int32_t long_t = split_threshold(flags);
   const bool fill = blk || runs || pos;
   int64_t cut = 0;
   // (sized as a handle with these options would: for the slice kernel when eligible)
@@ -366,7 +368,3 @@ int hspmv_xdict_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, unsigned f
 }
 
 }  // extern "C"
-
-namespace hspmv {
-
-}  // namespace hspmv
