@@ -437,6 +437,7 @@ static int fill_info(hspmv_handle *h, hspmv_info *out) {
   out->serial_order = 1;
   for (auto &sh : h->shards) out->serial_order &= sh.dp.serial_max == INT32_MAX ? 1 : 0;
   out->row_slices = s.dp.sl_desc ? 1 : 0;
+  out->slice_pos_bits = s.dp.sl_desc ? s.dp.sl_pos_bits : 0;
   if (s.plan.kernel == kCsort)
     for (int hh = 0; hh < 4; ++hh) out->csort_part_begin[hh] = s.csort_part_begin[hh];
   for (auto &sh : h->shards)

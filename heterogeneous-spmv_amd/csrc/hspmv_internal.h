@@ -246,11 +246,15 @@ struct DevPlan {
   // 64-row wave task column-major, one lane per row (hspmv_slices,
   // spmv_device.cuh).  sl_desc: {prefix, first row} per task and a closing
   // pair ({padded slot columns, m}); slice t's values start at sl_val + 64 *
-  // prefix elements, its positions at sl_pos + 64 * prefix; sl_len: one
-  // length per row.  Set only when the launch runs the slice kernel.
+  // prefix elements; sl_len: one length per row.  Positions: sl_pos_bits =
+  // 16, slice t's start at sl_pos + 64 * prefix; 12, the packed stream, slice
+  // t's at 128 * sl_ppre[t] bytes.  Set only when the launch runs the slice
+  // kernel.
   const int32_t *sl_desc = nullptr;
   const uint8_t *sl_len = nullptr;
   const uint16_t *sl_pos = nullptr;
+  const int32_t *sl_ppre = nullptr;
+  int32_t sl_pos_bits = 0;
   const void *sl_val = nullptr;
   int32_t n_slices = 0;  // descriptors (= wave tasks, the empty ones included)
   // x slabs (irregular gathers, x larger than an XCD's L2): the columns are

@@ -67,9 +67,12 @@ struct Shard {
   // dictionaries when the handle is eligible (hspmv_slices.cpp)
   int32_t *d_sl_desc = nullptr;
   uint8_t *d_sl_len = nullptr;
-  uint16_t *d_sl_pos = nullptr;
+  uint16_t *d_sl_pos = nullptr;   // the position stream: 16-bit, or packed (sl_pos_bits = 12)
+  int32_t *d_sl_ppre = nullptr;   // packed stream only: each slice's start in 128-byte units
   void *d_sl_val = nullptr;
   int64_t sl_bytes = 0, sl_desc_n = 0, sl_padded = 0;  // device bytes, descriptors, sum of slice widths
+  int sl_pos_bits = 0;            // 0 no slices, else 12 or 16 (hspmv_slices_pack)
+  int64_t sl_pos_bytes = 0;       // position bytes read per SpMV (the stream and d_sl_ppre)
   bool owns_csr = false;             // d_rp / d_ci / d_val are this shard's own uploads
   int32_t *d_slab_rp = nullptr;      // x slabs (build_xslabs): per-slab row pointers,
   int32_t *d_slab_col = nullptr;     // slab-major columns and values

@@ -60,6 +60,7 @@ void free_shard(Shard &s, bool borrowed) {
   (void)hipFree(s.d_sl_desc);
   (void)hipFree(s.d_sl_len);
   (void)hipFree(s.d_sl_pos);
+  (void)hipFree(s.d_sl_ppre);
   (void)hipFree(s.d_sl_val);
   (void)hipFree(s.d_slab_rp);
   (void)hipFree(s.d_slab_col);

@@ -31,6 +31,20 @@ namespace hspmv {
 // Rows are padded to their slice's longest row only (no alignment slots), and
 // the kernel masks the padding by the row length.
 //
+// That is the plan (build_slices, hspmv_slices_plan: the host view, in slot
+// order).  The device reads the positions packed (pack_slice_pos): when every
+// position of the handle is below 4096 -- every block dictionary holds at
+// most 4096 entries -- the floor(w / 8) whole 8-slot groups of a slice take 12
+// bytes per lane (eight 12-bit fields, little-endian in three dwords,
+// lane-major inside the group: one wave load is 768 contiguous bytes), and
+// the w mod 8 last slots stay 16-bit exactly as above (one 8-byte group when
+// w mod 8 >= 4, then single columns).  A slice's positions then take 128 * (6
+// floor(w / 8) + w mod 8) bytes, still 128-byte aligned, and start at 128 *
+// pos_prefix[s] bytes: a second prefix table beside the descriptors, which
+// stay as they are.  A handle with a larger dictionary, or one whose slices
+// are too narrow for the packing to pay for that table, keeps the 16-bit
+// stream (pos_prefix = the descriptors' prefix, not uploaded).
+//
 // Eligible (slices_why == HSPMV_SLICES_OK): dictionaries over the CSR3
 // aligned plan's tasks or STREAM's 64-row groups, no split rows, every row
 // within the dtype's serial bound, and the slice format's bytes per SpMV not
@@ -135,27 +149,103 @@ void build_slices(const int32_t *rp, const uint16_t *pos, const void *val, int64
   });
 }
 
+// 128-byte units of a slice of width w in the position stream.
+static inline int64_t pos_units(int32_t w, int bits) { return bits == 12 ? 6 * (w / 8) + w % 8 : w; }
+
+// 12 when every position of the plan fits 12 bits and the packed stream with
+// its prefix table is the smaller one (slices under 8 slots wide pack nothing:
+// such a handle keeps the 16-bit stream and no second table), else 16.
+static int slice_pos_bits(const int32_t *desc, int64_t nd, const uint16_t *pos) {
+  const int64_t n = 64 * (int64_t)desc[2 * nd];
+  uint16_t top = 0;
+  for (int64_t i = 0; i < n; ++i) top = std::max(top, pos[i]);
+  int64_t units12 = 0;
+  for (int64_t s = 0; s < nd; ++s) units12 += pos_units(desc[2 * s + 2] - desc[2 * s], 12);
+  return top < 4096 && 128 * units12 + 4 * (nd + 1) < 2 * n ? 12 : 16;
+}
+
+// The device position stream of a plan (desc, pos): prefix[s] = slice s's
+// start in 128-byte units (nd + 1 entries) and, when out is given, the
+// stream itself, 128 * prefix[nd] bytes.
+static void pack_slice_pos(const int32_t *desc, int64_t nd, const uint16_t *pos, int bits, int32_t *prefix,
+                    unsigned char *out) {
+  int64_t pre = 0;
+  for (int64_t s = 0; s < nd; ++s) {
+    prefix[s] = (int32_t)pre;
+    pre += pos_units(desc[2 * s + 2] - desc[2 * s], bits);
+  }
+  prefix[nd] = (int32_t)pre;
+  if (!out) return;
+  if (bits != 12) {
+    memcpy(out, pos, 128 * (size_t)pre);
+    return;
+  }
+  parallel_ranges(nd, 256, [&](int64_t s0, int64_t s1, int) {
+    for (int64_t s = s0; s < s1; ++s) {
+      const size_t base = 64 * (size_t)desc[2 * s];
+      const int32_t w = desc[2 * s + 2] - desc[2 * s], w8 = w / 8 * 8;
+      unsigned char *dst = out + 128 * (size_t)prefix[s];
+      for (int32_t g = 0; g < w / 8; ++g)
+        for (int i = 0; i < 64; ++i) {
+          uint64_t p[8];
+          for (int e = 0; e < 8; ++e) p[e] = pos[slot_at(base, w, 8 * g + e, i, 4)];
+          const uint64_t lo = p[0] | p[1] << 12 | p[2] << 24 | p[3] << 36 | p[4] << 48 | p[5] << 60;
+          const uint32_t d[3] = {(uint32_t)lo, (uint32_t)(lo >> 32),
+                                 (uint32_t)(p[5] >> 4 | p[6] << 8 | p[7] << 20)};
+          memcpy(dst + 768 * (size_t)g + 12 * (size_t)i, d, 12);
+        }
+      // the w mod 8 last slots: the 16-bit layout of a slice of that width
+      for (int32_t k = w8; k < w; ++k)
+        for (int i = 0; i < 64; ++i) {
+          const uint16_t v = pos[slot_at(base, w, k, i, 4)];
+          memcpy(dst + 96 * (size_t)w8 + 2 * slot_at(0, w - w8, k - w8, i, 4), &v, 2);
+        }
+    }
+  });
+}
+
 int upload_slices(Shard &s, const SlicePlan &P) {
   int rc;
+  const int64_t nd = (int64_t)P.desc.size() / 2 - 1;
+  int32_t bits = 0;
+  int64_t stream = 0;
+  if ((rc = hspmv_slices_pack(nd, P.desc.data(), P.pos.data(), &bits, &stream, nullptr, nullptr))) return rc;
+  size_t pos_bytes = 2 * P.pos.size(), table_bytes = 0;
+  if (bits == 12) {
+    std::vector<int32_t> prefix((size_t)nd + 1);
+    // 16 bytes past the stream: a 12-byte load widened to 16 stays inside
+    std::vector<unsigned char> packed((size_t)stream + 16, 0);
+    if ((rc = hspmv_slices_pack(nd, P.desc.data(), P.pos.data(), &bits, &stream, prefix.data(), packed.data())))
+      return rc;
+    pos_bytes = packed.size();
+    table_bytes = 4 * prefix.size();
+    if ((rc = upload(s, &s.d_sl_pos, packed.data(), pos_bytes))) return rc;
+    if ((rc = upload(s, &s.d_sl_ppre, prefix.data(), table_bytes))) return rc;
+  } else if ((rc = upload(s, &s.d_sl_pos, P.pos.data(), pos_bytes))) {  // the plan's stream as it is
+    return rc;
+  }
   if ((rc = upload(s, &s.d_sl_desc, P.desc.data(), 4 * P.desc.size()))) return rc;
   if ((rc = upload(s, &s.d_sl_len, P.len.data(), P.len.size()))) return rc;
-  if ((rc = upload(s, &s.d_sl_pos, P.pos.data(), 2 * P.pos.size()))) return rc;
   if ((rc = upload(s, &s.d_sl_val, P.val.data(), P.val.size()))) return rc;
-  s.sl_bytes = (int64_t)(4 * P.desc.size() + P.len.size() + 2 * P.pos.size() + P.val.size());
-  s.sl_desc_n = (int64_t)P.desc.size() / 2 - 1;
+  s.sl_bytes = (int64_t)(4 * P.desc.size() + P.len.size() + pos_bytes + table_bytes + P.val.size());
+  s.sl_desc_n = nd;
   s.sl_padded = P.padded;
+  s.sl_pos_bits = bits;
+  s.sl_pos_bytes = stream + (int64_t)table_bytes;
   return HSPMV_OK;
 }
 
 void drop_slices(Shard &s) {
-  for (void *p : {(void *)s.d_sl_desc, (void *)s.d_sl_len, (void *)s.d_sl_pos, s.d_sl_val})
+  for (void *p : {(void *)s.d_sl_desc, (void *)s.d_sl_len, (void *)s.d_sl_pos, (void *)s.d_sl_ppre, s.d_sl_val})
     if (p) (void)hipFree(p);
   if (s.d_sl_desc) s.bytes -= s.sl_bytes;
   s.d_sl_desc = nullptr;
   s.d_sl_len = nullptr;
   s.d_sl_pos = nullptr;
+  s.d_sl_ppre = nullptr;
   s.d_sl_val = nullptr;
   s.sl_bytes = 0;
+  s.sl_pos_bits = 0;
   s.A.has_slices = false;
 }
 
@@ -206,6 +296,21 @@ int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hsp
   if (len && A->m) memcpy(len, S.len.data(), (size_t)A->m);
   if (pos && S.padded) memcpy(pos, S.pos.data(), 2 * (size_t)(64 * S.padded));
   if (val && S.padded) memcpy(val, S.val.data(), dtype_size(A->dtype) * (size_t)(64 * S.padded));
+  return HSPMV_OK;
+}
+
+int hspmv_slices_pack(int64_t n_desc, const int32_t *desc, const uint16_t *pos, int32_t *bits,
+                      int64_t *pos_bytes, int32_t *pos_prefix, void *packed) {
+  clear_error();
+  if (n_desc < 0 || !desc || !pos || !bits || !pos_bytes) return set_error(HSPMV_E_INVALID, "NULL argument");
+  for (int64_t s = 0; s < n_desc; ++s)
+    if (desc[2 * s] < 0 || desc[2 * s + 2] < desc[2 * s]) return set_error(HSPMV_E_INVALID, "desc: prefixes decrease");
+  *bits = slice_pos_bits(desc, n_desc, pos);
+  std::vector<int32_t> prefix((size_t)n_desc + 1);
+  pack_slice_pos(desc, n_desc, pos, *bits, prefix.data(), nullptr);
+  *pos_bytes = 128 * (int64_t)prefix[(size_t)n_desc];
+  if (pos_prefix) memcpy(pos_prefix, prefix.data(), 4 * prefix.size());
+  if (packed) pack_slice_pos(desc, n_desc, pos, *bits, prefix.data(), (unsigned char *)packed);
   return HSPMV_OK;
 }
 

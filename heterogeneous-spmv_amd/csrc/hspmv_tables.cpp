@@ -795,6 +795,8 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags) {
       s.dp.sl_desc = s.d_sl_desc;
       s.dp.sl_len = s.d_sl_len;
       s.dp.sl_pos = s.d_sl_pos;
+      s.dp.sl_ppre = s.d_sl_ppre;
+      s.dp.sl_pos_bits = s.sl_pos_bits;
       s.dp.sl_val = s.d_sl_val;
       s.dp.n_slices = (int32_t)s.sl_desc_n;
       s.plan.row_slices = true;
@@ -805,7 +807,8 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags) {
         s.bytes -= (int64_t)(sv * (double)s.A.nnz);
       }
       s.c16_saved = (double)s.A.nnz * (sv + 4.0) + 4.0 * (double)(m + 1) -
-                    (64.0 * (double)s.sl_padded * (sv + 2.0) + (double)m + 8.0 * (double)(s.sl_desc_n + 1)) -
+                    (64.0 * (double)s.sl_padded * sv + (double)s.sl_pos_bytes + (double)m +
+                     8.0 * (double)(s.sl_desc_n + 1)) -
                     4.0 * (double)(s.xd_runs_n * 2) - 4.0 * (double)s.plan.blocks -
                     sv * (double)(s.xd_entries - s.x_entries);
     } else if (fits) {

@@ -220,6 +220,15 @@ __device__ __forceinline__ int64_t sload_i64(const void *p, uint64_t byte_off) {
   return *(ci64 *)(((uint64_t)hi << 32) | lo);
 }
 
+// The same for 4 bytes.
+__device__ __forceinline__ int32_t sload_i32(const void *p, uint64_t byte_off) {
+  const uint64_t v = reinterpret_cast<uint64_t>(p) + byte_off;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  typedef __attribute__((address_space(4))) const int32_t ci32;
+  return *(ci32 *)(((uint64_t)hi << 32) | lo);
+}
+
 // Ordered sum of lds[lo..hi) into acc, left to right: the LDS reads are
 // issued 4 at a time (one LDS latency per 4 nonzeros instead of per nonzero),
 // the last 1-3 together (C4's 10-nonzero rows: 54.2 -> 51.7 us,
@@ -715,6 +724,11 @@ __global__ __launch_bounds__(W * 64) void hspmv_csr3(
 // wave_sync and no row pointers.  Slot k of a slice starts at element 64 * k
 // of the slice in both streams (groups and the trailing single columns
 // alike).  Slots past a row's end are masked by its length, never added.
+//
+// PB = 12 (a handle whose positions all fit 12 bits, hspmv_slices_pack): a
+// whole batch of 8 slots reads one 12-byte position group per lane, eight
+// 12-bit fields, at 96 bytes per slot column; the slice's last w mod 8 slots
+// follow in the 16-bit layout, and the slice starts at 128 * ppre[t] bytes.
 #ifndef HSPMV_SLICE_BATCH
 #define HSPMV_SLICE_BATCH 8  // slots per load batch (a multiple of 4)
 #endif
@@ -723,6 +737,7 @@ struct Slices {
   const int32_t *desc;  // {prefix, first row} per task, closed by {total, m}
   const uint8_t *len;   // nonzeros per row
   const uint16_t *pos;  // dictionary positions, 64 * prefix elements per slice start
+  const int32_t *ppre;  // PB = 12: the packed positions' start per task, 128-byte units
 };
 
 typedef int32_t sl_i4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -736,48 +751,62 @@ __device__ __forceinline__ sl_i4 sload_i128(const void *p, uint64_t byte_off) {
   return *(ci128 *)(((uint64_t)hi << 32) | lo);
 }
 
+typedef uint32_t sl_u3 __attribute__((ext_vector_type(3), aligned(4)));
+
 template <typename T, int B>
 struct SliceBatch {
   T v[B];               // slot k0 + i of the lane's row
-  uint32_t pq[B / 2];   // positions of whole 4-slot groups, two per register
+  uint32_t pq[B / 2];   // positions of whole 4-slot groups, two per register (PB = 12: 3 per 8 slots)
   uint32_t ps[3];       // positions of the slice's last 1-3 slots (single columns)
 };
 
 // A whole batch: slots [k0, k0 + B) all lie in 16-byte value groups and
-// 8-byte position groups.  vb / pb: the slice's streams.
-template <typename T, bool NT, int B>
+// 8-byte (PB = 12: 12-byte) position groups.  vb / pb: the slice's streams.
+template <typename T, bool NT, int B, int PB>
 __device__ __forceinline__ void slice_load_full(SliceBatch<T, B> &q, const gchar *vb, const gchar *pb,
                                                 int32_t k0, int lane) {
   constexpr int G = 16 / (int)sizeof(T);
   typedef T tv __attribute__((ext_vector_type(G)));
   typedef uint32_t u2 __attribute__((ext_vector_type(2)));
   const gchar *vbb = vb + (uint64_t)(uint32_t)k0 * (kWave * sizeof(T));
-  const gchar *pbb = pb + (uint64_t)(uint32_t)k0 * (kWave * 2u);
+  const gchar *pbb = pb + (uint64_t)(uint32_t)k0 * (kWave * PB / 8u);
 #pragma unroll
   for (int j = 0; j < B / G; ++j) {
     const tv t = ld_off<NT, tv>(vbb, (uint32_t)(j * kWave + lane) * 16u);
 #pragma unroll
     for (int e = 0; e < G; ++e) q.v[j * G + e] = t[e];
   }
+  if constexpr (PB == 12) {
+    // (sizeof(sl_u3) is 16: the groups are addressed in bytes)
 #pragma unroll
-  for (int g = 0; g < B / 4; ++g) {
-    const u2 t = ld_off<NT, u2>(pbb, (uint32_t)(g * kWave + lane) * 8u);
-    q.pq[2 * g] = t[0];
-    q.pq[2 * g + 1] = t[1];
+    for (int g = 0; g < B / 8; ++g) {
+      const sl_u3 t = ld_off<NT, sl_u3>(pbb, (uint32_t)(g * kWave + lane) * 12u);
+      q.pq[3 * g] = t[0];
+      q.pq[3 * g + 1] = t[1];
+      q.pq[3 * g + 2] = t[2];
+    }
+  } else {
+#pragma unroll
+    for (int g = 0; g < B / 4; ++g) {
+      const u2 t = ld_off<NT, u2>(pbb, (uint32_t)(g * kWave + lane) * 8u);
+      q.pq[2 * g] = t[0];
+      q.pq[2 * g + 1] = t[1];
+    }
   }
 }
 
 // The slice's last, partial batch: slots [k0, w), w - k0 < B; whole groups
 // as above, the rest from the single columns.  Slots past w read as value 0
-// at position 0 (and are masked like every slot past a row's end).
-template <typename T, bool NT, int B>
+// at position 0 (and are masked like every slot past a row's end).  The
+// tail's positions are 16-bit for either PB; PB sets where they start.
+template <typename T, bool NT, int B, int PB>
 __device__ __forceinline__ void slice_load_tail(SliceBatch<T, B> &q, const gchar *vb, const gchar *pb,
                                                 int32_t k0, int32_t w, int lane) {
   constexpr int G = 16 / (int)sizeof(T);
   typedef T tv __attribute__((ext_vector_type(G)));
   typedef uint32_t u2 __attribute__((ext_vector_type(2)));
   const gchar *vbb = vb + (uint64_t)(uint32_t)k0 * (kWave * sizeof(T));
-  const gchar *pbb = pb + (uint64_t)(uint32_t)k0 * (kWave * 2u);
+  const gchar *pbb = pb + (uint64_t)(uint32_t)k0 * (kWave * PB / 8u);
 #pragma unroll
   for (int i = 0; i < B; ++i) q.v[i] = T(0);
 #pragma unroll
@@ -812,18 +841,31 @@ __device__ __forceinline__ void slice_load_tail(SliceBatch<T, B> &q, const gchar
   }
 }
 
+// Position of slot i of a whole batch.
+template <int PB>
+__device__ __forceinline__ uint32_t slice_pos(const uint32_t *pq, int i) {
+  if constexpr (PB == 12) {
+    const int d = 3 * (i / 8) + 12 * (i % 8) / 32, sh = 12 * (i % 8) % 32;
+    uint32_t v = pq[d] >> sh;
+    if (sh > 20) v |= pq[d + 1] << (32 - sh);
+    return v & 0xfffu;
+  } else {
+    return (pq[i / 2] >> (16 * (i & 1))) & 0xffffu;
+  }
+}
+
 // Adds the batch's slots to acc in slot order: the product rounded on its
 // own (-ffp-contract=off), then the add; a slot at or past the row's end
-// leaves acc as it is.  full: every position comes from pq.
-template <typename T, int B>
+// leaves acc as it is.  full: every position comes from pq, PB bits each
+// (a tail batch's are 16-bit).
+template <typename T, int B, int PB>
 __device__ __forceinline__ T slice_consume(T acc, const SliceBatch<T, B> &q, const T *xs, int32_t k0,
                                            int32_t w, int32_t len, bool full) {
   T xv[B];
 #pragma unroll
   for (int i = 0; i < B; ++i) {
     const int g = i / 4, r = i % 4;
-    const uint32_t packed = (q.pq[2 * g + r / 2] >> (16 * (r & 1))) & 0xffffu;
-    const uint32_t p = (full || k0 + 4 * g + 4 <= w) ? packed : q.ps[r < 3 ? r : 0];
+    const uint32_t p = (full || k0 + 4 * g + 4 <= w) ? slice_pos<PB>(q.pq, i) : q.ps[r < 3 ? r : 0];
     xv[i] = xs[p];
   }
 #pragma unroll
@@ -840,23 +882,25 @@ __device__ __forceinline__ T slice_consume(T acc, const SliceBatch<T, B> &q, con
 // rows' lengths before the staging; after the barrier it walks the slot
 // columns in batches of B, the next batch's loads issued before the current
 // one is consumed.  LDS: the dictionary alone.
-template <typename T, bool NT, int B>
+template <typename T, bool NT, int B, int PB>
 __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t xcd_chunk, int32_t y_nt,
                                                     Slices sl, XDict xd, const T *__restrict__ val,
                                                     const T *__restrict__ x, T *__restrict__ y) {
   static_assert(B % 4 == 0 && B >= 4, "batches hold whole position groups");
+  static_assert(PB == 16 || (PB == 12 && B % 8 == 0), "12-bit positions come in groups of 8 slots");
   extern __shared__ __attribute__((aligned(16))) unsigned char xdyn[];
   const int wid = threadIdx.x >> 6;
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t blk = xcd_chunk_remap(blockIdx.x, gridDim.x, xcd_chunk);
   const int64_t t = blk * 4 + wid;
-  int32_t off = 0, w = 0, r0 = 0, nr = 0;
+  int32_t off = 0, poff = 0, w = 0, r0 = 0, nr = 0;
   if (t < n_slices) {  // wave-uniform
     const sl_i4 d = sload_i128(sl.desc, (uint64_t)t * 8u);
     off = d[0];
     r0 = d[1];
     w = d[2] - d[0];
     nr = d[3] - d[1];
+    poff = PB == 12 ? sload_i32(sl.ppre, (uint64_t)t * 4u) : off;
   }
   int32_t len = 0;
   if (lane < nr) len = (int32_t)sl.len[r0 + lane];
@@ -864,35 +908,35 @@ __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t x
   if (nr <= 0) return;
   const T *xs = reinterpret_cast<const T *>(xdyn);
   const gchar *vb = uniform_ptr(val + (int64_t)off * kWave);
-  const gchar *pb = uniform_ptr(sl.pos + (int64_t)off * kWave);
+  const gchar *pb = uniform_ptr(sl.pos + (int64_t)poff * kWave);
   const int32_t wf = w & ~(B - 1);  // slots in whole batches
   T acc = T(0);
   SliceBatch<T, B> cur, nxt, tail;
   int32_t k0 = 0;
-  if (wf > 0) slice_load_full<T, NT, B>(cur, vb, pb, 0, lane);
+  if (wf > 0) slice_load_full<T, NT, B, PB>(cur, vb, pb, 0, lane);
   for (; k0 + 3 * B <= wf; k0 += 2 * B) {
-    slice_load_full<T, NT, B>(nxt, vb, pb, k0 + B, lane);
+    slice_load_full<T, NT, B, PB>(nxt, vb, pb, k0 + B, lane);
     __builtin_amdgcn_sched_barrier(0);
-    acc = slice_consume<T, B>(acc, cur, xs, k0, w, len, true);
+    acc = slice_consume<T, B, PB>(acc, cur, xs, k0, w, len, true);
     __builtin_amdgcn_sched_barrier(0);
-    slice_load_full<T, NT, B>(cur, vb, pb, k0 + 2 * B, lane);
+    slice_load_full<T, NT, B, PB>(cur, vb, pb, k0 + 2 * B, lane);
     __builtin_amdgcn_sched_barrier(0);
-    acc = slice_consume<T, B>(acc, nxt, xs, k0 + B, w, len, true);
+    acc = slice_consume<T, B, PB>(acc, nxt, xs, k0 + B, w, len, true);
     __builtin_amdgcn_sched_barrier(0);
   }
   if (k0 + 2 * B <= wf) {
-    slice_load_full<T, NT, B>(nxt, vb, pb, k0 + B, lane);
+    slice_load_full<T, NT, B, PB>(nxt, vb, pb, k0 + B, lane);
     __builtin_amdgcn_sched_barrier(0);
-    acc = slice_consume<T, B>(acc, cur, xs, k0, w, len, true);
+    acc = slice_consume<T, B, PB>(acc, cur, xs, k0, w, len, true);
     __builtin_amdgcn_sched_barrier(0);
     cur = nxt;
     k0 += B;
   }
   // cur: the last whole batch (at wf - B), not yet added
-  if (w > wf) slice_load_tail<T, NT, B>(tail, vb, pb, wf, w, lane);
+  if (w > wf) slice_load_tail<T, NT, B, PB>(tail, vb, pb, wf, w, lane);
   __builtin_amdgcn_sched_barrier(0);
-  if (wf > 0) acc = slice_consume<T, B>(acc, cur, xs, wf - B, w, len, true);
-  if (w > wf) acc = slice_consume<T, B>(acc, tail, xs, wf, w, len, false);
+  if (wf > 0) acc = slice_consume<T, B, PB>(acc, cur, xs, wf - B, w, len, true);
+  if (w > wf) acc = slice_consume<T, B, 16>(acc, tail, xs, wf, w, len, false);
   if constexpr ((HSPMV_DIAG & 256) != 0) {  // ablation: no y stores (kept live)
     if (lane < nr && acc == T(12345.678)) y[r0 + lane] = acc;
   } else if (lane < nr) {
@@ -905,21 +949,30 @@ __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t x
 
 // ------------------------------------------------------------------ launchers
 
-template <typename T>
-hipError_t launch_slices(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st) {
-  if (!dp.xd_blk || !dp.sl_len || !dp.sl_pos || !dp.sl_val || p.waves_per_block != 4 ||
-      p.blocks != ((int64_t)dp.n_slices + 3) / 4)
-    return hipErrorInvalidValue;  // the host built the slices for another block shape
-  const Slices sl{dp.sl_desc, dp.sl_len, dp.sl_pos};
+template <typename T, int PB>
+void launch_slices_pb(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st) {
+  const Slices sl{dp.sl_desc, dp.sl_len, dp.sl_pos, dp.sl_ppre};
   const XDict xd{dp.xd_blk, reinterpret_cast<const int2 *>(dp.xd_runs)};
   const unsigned dyn = (unsigned)dp.xd_lds_bytes + (unsigned)p.dyn_lds;
   const T *val = static_cast<const T *>(dp.sl_val);
   if (p.nontemporal)
-    hipLaunchKernelGGL((hspmv_slices<T, true, HSPMV_SLICE_BATCH>), dim3((unsigned)p.blocks), dim3(256), dyn, st,
-                       dp.n_slices, (uint32_t)p.xcd_chunk, (int32_t)p.y_nt, sl, xd, val, x, y);
+    hipLaunchKernelGGL((hspmv_slices<T, true, HSPMV_SLICE_BATCH, PB>), dim3((unsigned)p.blocks), dim3(256), dyn,
+                       st, dp.n_slices, (uint32_t)p.xcd_chunk, (int32_t)p.y_nt, sl, xd, val, x, y);
   else
-    hipLaunchKernelGGL((hspmv_slices<T, false, HSPMV_SLICE_BATCH>), dim3((unsigned)p.blocks), dim3(256), dyn, st,
-                       dp.n_slices, (uint32_t)p.xcd_chunk, (int32_t)p.y_nt, sl, xd, val, x, y);
+    hipLaunchKernelGGL((hspmv_slices<T, false, HSPMV_SLICE_BATCH, PB>), dim3((unsigned)p.blocks), dim3(256), dyn,
+                       st, dp.n_slices, (uint32_t)p.xcd_chunk, (int32_t)p.y_nt, sl, xd, val, x, y);
+}
+
+template <typename T>
+hipError_t launch_slices(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st) {
+  if (!dp.xd_blk || !dp.sl_len || !dp.sl_pos || !dp.sl_val || p.waves_per_block != 4 ||
+      p.blocks != ((int64_t)dp.n_slices + 3) / 4 ||
+      !(dp.sl_pos_bits == 16 || (dp.sl_pos_bits == 12 && dp.sl_ppre)))
+    return hipErrorInvalidValue;  // the host built the slices for another block shape
+  if (dp.sl_pos_bits == 12)
+    launch_slices_pb<T, 12>(dp, p, x, y, st);
+  else
+    launch_slices_pb<T, 16>(dp, p, x, y, st);
   return hipGetLastError();
 }
 

@@ -39,13 +39,14 @@
 //      sub-warp per row inside (8,12)-thread blocks, csrk.cu:185-319) and
 //      cuSpMV_2 (degenerate outer level).
 //
-//  * hspmv_slices<T, NT, B>       (STREAM / CSR3 handles with row slices)
+//  * hspmv_slices<T, NT, B, PB>   (STREAM / CSR3 handles with row slices)
 //      the transposed shape of the two kernels above for dictionary handles
 //      whose rows are all summed serially: the wave's 64-row task is stored
 //      slot-major (hspmv_slices.cpp), lane i multiplies and adds row i left
-//      to right out of 16-byte value and 8-byte position loads, B slots per
-//      batch, the next batch in flight.  Same bits, no product buffer, no
-//      row pointers (spmv_device.cuh "row slices").
+//      to right out of 16-byte value and 8-byte position loads (PB = 12,
+//      dictionaries of <= 4096 entries: one 12-byte load of eight 12-bit
+//      positions), B slots per batch, the next batch in flight.  Same bits,
+//      no product buffer, no row pointers (spmv_device.cuh "row slices").
 //
 //  * hspmv_csr_vector<T, L, NT>   (HSPMV_KERNEL_VECTOR)
 //      L lanes (a sub-wave, L | 64) per row, lanes stride the row's nonzeros

@@ -124,7 +124,7 @@ class Info(C.Structure):
                 # since 1.1
                 ("csort_fixed_point", C.c_int32), ("serial_order", C.c_int32),
                 ("csort_part_begin", C.c_int64 * 4),
-                ("row_slices", C.c_int32), ("reserved1", C.c_int32)]
+                ("row_slices", C.c_int32), ("slice_pos_bits", C.c_int32)]
 
 
 CSR3_PLANS = {"auto": 0, "aligned": 1, "packed": 2, "ssr": 3}
@@ -227,6 +227,7 @@ SIGNATURES = {
     "hspmv_slices_plan": (C.c_int, [C.POINTER(Csr), C.POINTER(Csr3Maps), C.POINTER(Options),
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int32), _P, _P, _P, _P]),
+    "hspmv_slices_pack": (C.c_int, [C.c_int64, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P, _P]),
     "hspmv_alg_bytes": (C.c_double, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64]),
     "hspmv_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "hspmv_rccl_version": (C.c_int, [C.POINTER(C.c_int)]),

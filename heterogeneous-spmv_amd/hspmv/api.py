@@ -325,6 +325,26 @@ def slices_plan(A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, kernel: str = 
     return out
 
 
+def slices_pack(desc: np.ndarray, pos: np.ndarray) -> dict:
+    """The position stream a handle uploads for slices_plan's ``desc`` and
+    ``pos`` (hspmv_slices_pack): ``bits`` (12 or 16), ``pos_prefix`` (each
+    slice's start in 128-byte units, n_desc + 1 entries) and ``packed`` (the
+    stream's bytes)."""
+    desc = np.ascontiguousarray(desc, dtype=np.int32).reshape(-1, 2)
+    pos = np.ascontiguousarray(pos, dtype=np.uint16)
+    nd = desc.shape[0] - 1
+    if nd < 0 or pos.shape[0] < 64 * int(desc[nd, 0]):
+        raise ValueError("slices_pack: pos is shorter than desc's 64 * total width")
+    bits, nbytes = C.c_int32(), C.c_int64()
+    L = lib()
+    args = (nd, _ptr(desc), _ptr(pos), C.byref(bits), C.byref(nbytes))
+    check(L.hspmv_slices_pack(*args, None, None), "slices_pack")
+    prefix = np.empty(nd + 1, np.int32)
+    packed = np.zeros(max(nbytes.value, 1), np.uint8)
+    check(L.hspmv_slices_pack(*args, _ptr(prefix), _ptr(packed)), "slices_pack")
+    return {"bits": bits.value, "pos_prefix": prefix, "packed": packed[:nbytes.value]}
+
+
 def alg_bytes(m: int, n: int, nnz: int, dtype, n_ssr: int = 0, n_sr: int = 0) -> float:
     return float(lib().hspmv_alg_bytes(m, n, nnz, dtype_code(dtype), n_ssr, n_sr))
 

@@ -209,7 +209,9 @@ typedef struct {
                                (hspmv_options.row_slices); kernel, x_dict and
                                the other fields read as for the chunked kernel,
                                format_bytes counts the slice format          */
-  int32_t reserved1;
+  int32_t slice_pos_bits;   /* bits per dictionary position in the row slices'
+                               whole 8-slot groups (hspmv_slices_pack): 12 or
+                               16; 0 without row slices (GPU 0)              */
 } hspmv_info;
 
 typedef struct hspmv_handle hspmv_handle;
@@ -572,6 +574,24 @@ int hspmv_xdict_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, unsigned f
 int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt,
                       int64_t *n_desc, int64_t *n_slices, int64_t *padded_entries, int32_t *why,
                       int32_t *desc, uint8_t *len, uint16_t *pos, void *val);
+/* The position stream a handle uploads for the row slices {desc, pos} of
+ * hspmv_slices_plan (n_desc + 1 descriptor pairs, 64 * desc[2 n_desc]
+ * positions).  *bits = 12 when every position is below 4096 (every block
+ * dictionary holds at most 4096 entries) and the packed stream with its
+ * prefix table is smaller than pos (some slices are 8 or more slots wide),
+ * else 16.  With 12, the floor(w / 8)
+ * whole 8-slot groups of a slice of width w take 12 bytes per lane -- slots
+ * 8 g .. 8 g + 7 of lane i as 12-bit fields, slot 8 g + e in bits 12 e .. 12 e
+ * + 11 of the little-endian 96-bit word at byte 768 g + 12 i of the slice --
+ * and the w mod 8 last slots follow as 16-bit positions laid out as
+ * hspmv_slices_plan lays out a slice of width w mod 8.  With 16 the stream is
+ * pos itself.  Slice s starts at byte 128 * pos_prefix[s]; pos_prefix (n_desc
+ * + 1 entries) sums 6 floor(w / 8) + w mod 8 (16 bits: w) over the earlier
+ * slices, *pos_bytes = 128 * pos_prefix[n_desc].  Call with NULL pos_prefix
+ * and packed for bits and pos_bytes.  Values, lengths and descriptors are
+ * hspmv_slices_plan's. */
+int hspmv_slices_pack(int64_t n_desc, const int32_t *desc, const uint16_t *pos, int32_t *bits,
+                      int64_t *pos_bytes, int32_t *pos_prefix, void *packed);
 double hspmv_alg_bytes(int64_t m, int64_t n, int64_t nnz, int dtype,
                        int64_t n_ssr, int64_t n_sr);
 int hspmv_device_count(int *count);
