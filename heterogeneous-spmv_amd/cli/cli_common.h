@@ -29,6 +29,9 @@
 //   --serial            every row summed in omp_spmv's order, one lane per
 //                       row: y bit-identical to the serial check (reported
 //                       as "Bitwise:")
+//   --sweep forward|alternate   the row kernel's block sweep from one SpMV to
+//                       the next (hspmv_set_sweep; default: the library's
+//                       choice; y is the same bits either way)
 //   --dump-y PATH       write y as raw binary (dtype) for external checks
 //   --no-check          skip the serial CPU check
 #pragma once
@@ -55,6 +58,7 @@ struct Options {
   bool nt = false;
   int plan = HSPMV_CSR3_PLAN_AUTO;
   int deterministic = 0;  // hspmv_options.deterministic
+  int sweep = HSPMV_SWEEP_AUTO;  // hspmv_set_sweep
   bool check = true;
   std::string dump_y;
   std::string params = "mi355x";
@@ -114,6 +118,11 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
       o.deterministic = HSPMV_DETERMINISTIC_REPRODUCIBLE;
     } else if (a == "--serial") {
       o.deterministic = HSPMV_DETERMINISTIC_SERIAL;
+    } else if (a == "--sweep") {
+      const char *v = need("--sweep"); if (!v) return false;
+      if (!strcmp(v, "forward")) o.sweep = HSPMV_SWEEP_FORWARD;
+      else if (!strcmp(v, "alternate")) o.sweep = HSPMV_SWEEP_ALTERNATE;
+      else { fprintf(stderr, "bad --sweep %s\n", v); return false; }
     } else if (a == "--no-check") {
       o.check = false;
     } else if (a == "--dump-y") {
@@ -215,6 +224,7 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
   opt.deterministic = o.deterministic;
   if (hspmv_create_ex(&h, &view, mv.n_ssr > 0 ? &mv : nullptr, &opt) != HSPMV_OK)
     return die("hspmv_create_ex");
+  if (o.sweep != HSPMV_SWEEP_AUTO && hspmv_set_sweep(h, o.sweep) != HSPMV_OK) return die("hspmv_set_sweep");
   std::vector<double> x64;
   fill_x(o, A.n, x64);
   if (perm) {

@@ -114,6 +114,24 @@ int create_single(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *
   return HSPMV_OK;
 }
 
+// Whether this shard's row kernel changes direction from one SpMV to the
+// next (hspmv_set_sweep).  The vector and column-sorted kernels never do.
+// AUTO: a single row-kernel launch (no x slabs) over a matrix the Infinity
+// Cache does not hold whole -- a resident one is served from it in either
+// direction.
+bool shard_alternates(const hspmv_handle *h, const Shard &s) {
+  if (h->sweep_mode == HSPMV_SWEEP_FORWARD || s.A.m == 0) return false;
+  if (s.plan.kernel != kStream && s.plan.kernel != kCsr3) return false;
+  if (h->sweep_mode == HSPMV_SWEEP_ALTERNATE) return true;
+  return s.dp.n_slabs == 0 && !mall_resident(s.A.m, h->n, s.A.nnz, h->dtype);
+}
+
+// The direction of the next SpMV on s; the caller flips h->sweep_phase once
+// per call, after every shard has been launched.
+bool shard_reverse(const hspmv_handle *h, const Shard &s) {
+  return h->sweep_phase && shard_alternates(h, s);
+}
+
 int check_devices(const int *devices, int n, int *ndev_out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
@@ -274,10 +292,34 @@ int hspmv_spmv(hspmv_handle *h) {
   if (!h->x_set) return set_error(HSPMV_E_STATE, "x not set (hspmv_set_x / hspmv_bind_x_device)");
   for (auto &s : h->shards) {
     HIP_TRY(hipSetDevice(s.device));
-    hipError_t e = launch_spmv(s.A, s.dp, h->dtype, s.plan, s.x, s.y, s.stream);
+    hipError_t e = launch_spmv(s.A, s.dp, h->dtype, s.plan, s.x, s.y, s.stream, shard_reverse(h, s));
     if (e != hipSuccess)
       return set_error(HSPMV_E_HIP, "SpMV launch on GPU %d failed: %s", s.device, hipGetErrorString(e));
   }
+  h->sweep_phase = !h->sweep_phase;
+  return HSPMV_OK;
+}
+
+int hspmv_set_sweep(hspmv_handle *h, int mode) {
+  clear_error();
+  int rc;
+  if ((rc = check_handle(h))) return rc;
+  if (mode != HSPMV_SWEEP_AUTO && mode != HSPMV_SWEEP_FORWARD && mode != HSPMV_SWEEP_ALTERNATE)
+    return set_error(HSPMV_E_INVALID, "sweep mode %d (HSPMV_SWEEP_AUTO, _FORWARD or _ALTERNATE)", mode);
+  h->sweep_mode = mode;
+  return HSPMV_OK;
+}
+
+int hspmv_block_order(int64_t n_blocks, int32_t xcd_chunk, int reverse, int32_t *order) {
+  clear_error();
+  if (n_blocks < 0 || n_blocks > INT32_MAX || xcd_chunk < 0 || (n_blocks > 0 && !order))
+    return set_error(HSPMV_E_INVALID, "bad block-order arguments");
+  // a chunk with no full span of 8 * chunk blocks is the dispatch order (and
+  // 8 * chunk stays inside 32 bits for the ones that reach the remap)
+  const uint32_t chunk = (int64_t)xcd_chunk * kNumXcd > n_blocks ? 1u : (uint32_t)xcd_chunk;
+  const uint32_t arg = chunk | (reverse ? kSweepReverse : 0u);
+  for (int64_t b = 0; b < n_blocks; ++b)
+    order[b] = (int32_t)sweep_block((uint32_t)b, (uint32_t)n_blocks, arg);
   return HSPMV_OK;
 }
 
@@ -307,11 +349,12 @@ int hspmv_run(hspmv_handle *h, int warmup, int iters, hspmv_timing *out) {
     for (auto &s : h->shards) {
       HIP_TRY(hipSetDevice(s.device));
       HIP_TRY(hipEventRecord(s.ev0, s.stream));
-      hipError_t e = launch_spmv(s.A, s.dp, h->dtype, s.plan, s.x, s.y, s.stream);
+      hipError_t e = launch_spmv(s.A, s.dp, h->dtype, s.plan, s.x, s.y, s.stream, shard_reverse(h, s));
       if (e != hipSuccess)
         return set_error(HSPMV_E_HIP, "SpMV launch failed: %s", hipGetErrorString(e));
       HIP_TRY(hipEventRecord(s.ev1, s.stream));
     }
+    h->sweep_phase = !h->sweep_phase;
     double dev = 0.0;
     for (auto &s : h->shards) {
       HIP_TRY(hipSetDevice(s.device));
@@ -438,6 +481,7 @@ static int fill_info(hspmv_handle *h, hspmv_info *out) {
   for (auto &sh : h->shards) out->serial_order &= sh.dp.serial_max == INT32_MAX ? 1 : 0;
   out->row_slices = s.dp.sl_desc ? 1 : 0;
   out->slice_pos_bits = s.dp.sl_desc ? s.dp.sl_pos_bits : 0;
+  out->sweep = shard_alternates(h, s) ? 1 : 0;
   if (s.plan.kernel == kCsort)
     for (int hh = 0; hh < 4; ++hh) out->csort_part_begin[hh] = s.csort_part_begin[hh];
   for (auto &sh : h->shards)

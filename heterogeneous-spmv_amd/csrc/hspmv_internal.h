@@ -137,6 +137,45 @@ inline bool mall_resident(int64_t m, int64_t n, int64_t nnz, int dtype) {
 // it miss L2.
 constexpr double kXcdL2Bytes = 4.0 * 1024 * 1024;
 
+// ---- the row kernels' block order: one definition for the kernels and the
+// host (hspmv_block_order, tests/test_sweep.py)
+#if defined(__HIPCC__)
+#define HSPMV_HD __host__ __device__ __forceinline__
+#else
+#define HSPMV_HD inline
+#endif
+constexpr uint32_t kNumXcd = 8;
+
+// Bijective XCD-aware block order (cdna_hip_programming.md §5 "XCD swizzle
+// must be bijective").  Blocks b and b+8 share an XCD under round-robin
+// dispatch; with chunk s > 1 each XCD takes s consecutive logical blocks in
+// turn, so at any moment the 8 XCDs work on 8 adjacent runs of s blocks:
+// s = nb/8 gives each XCD one contiguous eighth of the rows (x stays in
+// that XCD's L2), small s keeps the whole chip's read front compact (HBM
+// page locality) while rows still share x lines within an XCD.  s <= 1 is
+// the dispatch order.  Blocks past the last full 8*s span keep their index.
+HSPMV_HD uint32_t xcd_chunk_remap(uint32_t b, uint32_t nb, uint32_t s) {
+  if (s <= 1) return b;
+  const uint32_t span = kNumXcd * s;
+  if (b >= (nb / span) * span) return b;
+  const uint32_t i = b / kNumXcd, x = b % kNumXcd;
+  return (i / s) * span + x * s + (i % s);
+}
+
+// The sweep direction rides in the top bit of the kernels' block-order
+// argument (the chunk is at most 2^30): set, the remapped order is mirrored,
+// grid index b runs logical block nb - 1 - remap(b).  The mirror comes after
+// the remap, so consecutive logical blocks still share an XCD turn and the
+// rows of y are the same bits: a row's sum never leaves its block.  A launch
+// that sweeps the matrix against the direction of the one before it starts
+// on the bytes that one touched last, which the 256 MiB Infinity Cache still
+// holds (hspmv_set_sweep).
+constexpr uint32_t kSweepReverse = 0x80000000u;
+HSPMV_HD uint32_t sweep_block(uint32_t b, uint32_t nb, uint32_t order) {
+  const uint32_t blk = xcd_chunk_remap(b, nb, order & ~kSweepReverse);
+  return (order & kSweepReverse) ? nb - 1u - blk : blk;
+}
+
 // The fields of hspmv_options.flags (include/hspmv.h): the kernel code,
 // HSPMV_LANES(l), HSPMV_U(u) (5 bits below HSPMV_FLAG_PREFETCH),
 // HSPMV_XCD_CHUNK(s) (5 bits; 0 = automatic) and HSPMV_GROUPS(g) (3 bits; 1
@@ -280,6 +319,7 @@ struct LaunchPlan {
   bool y_nt = false;       // STREAM/CSR3: nontemporal y stores
   int32_t dyn_lds = 0;     // extra dynamic LDS per block (occupancy experiments)
   int32_t xcd_chunk = 1;   // blocks per XCD turn (1 = dispatch order; see xcd_chunk_remap)
+  bool reverse = false;    // STREAM/CSR3/slices: this launch sweeps the blocks last to first (launch_spmv)
   int32_t groups = 1;      // STREAM: 64-row groups per wave (next group's rp prefetched)
   int32_t carry = 0;       // STREAM/CSR3: rows start from y (x-slab passes after the first)
   bool lds_pad = false;     // STREAM: bank-padded product buffers (spmv_device.cuh lds_ix)
@@ -311,7 +351,10 @@ hipError_t launch_rows_f64(const DevCSR &A, const DevPlan &dp, const LaunchPlan 
 hipError_t launch_csort(const DevCsort &c, int dtype, const void *x, void *y, hipStream_t st);
 
 // Enqueues one y = A*x (main kernel + split-row kernels when present).
+// reverse: the STREAM / CSR3 / slice row kernel (each x-slab pass of it)
+// sweeps its blocks last to first; the launches keep their order, and the
+// vector, column-sorted and split-row kernels always run forward.
 hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, const LaunchPlan &plan,
-                       const void *x, void *y, hipStream_t stream);
+                       const void *x, void *y, hipStream_t stream, bool reverse = false);
 
 }  // namespace hspmv

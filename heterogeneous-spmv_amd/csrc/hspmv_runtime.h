@@ -142,6 +142,10 @@ struct hspmv_handle {
   }
   std::vector<ncclComm_t> comms;
   int rccl_version = 0;   // ncclGetVersion of the RCCL this process resolved
+  // hspmv_set_sweep: the mode, and the parity of the SpMV calls so far (one
+  // flip per hspmv_spmv / hspmv_run iteration, the same for every shard)
+  int sweep_mode = HSPMV_SWEEP_AUTO;
+  bool sweep_phase = false;
 };
 
 namespace hspmv {

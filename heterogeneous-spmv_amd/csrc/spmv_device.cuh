@@ -70,7 +70,6 @@ constexpr int kWave = 64;
 // The kernels take the bound as an argument (DevPlan.serial_max): kSerialMax,
 // or INT32_MAX for hspmv_options.deterministic = 3, where every row is summed
 // serially -- omp_spmv's order for every row, the long ones by one lane.
-constexpr int kNumXcd = 8;
 
 // PAD: a wave's product buffer holds chunk position i at lds_ix(i) = i + i /
 // 32 -- one pad element per 32 -- so that the lanes of an ordered sum, each
@@ -166,21 +165,8 @@ __device__ __forceinline__ T wave_sum_dpp(T v) {
   return lane_value(v, 63);
 }
 
-// Bijective XCD-aware block order (cdna_hip_programming.md §5 "XCD swizzle
-// must be bijective").  Blocks b and b+8 share an XCD under round-robin
-// dispatch; with chunk s > 1 each XCD takes s consecutive logical blocks in
-// turn, so at any moment the 8 XCDs work on 8 adjacent runs of s blocks:
-// s = nb/8 gives each XCD one contiguous eighth of the rows (x stays in
-// that XCD's L2), small s keeps the whole chip's read front compact (HBM
-// page locality) while rows still share x lines within an XCD.  s <= 1 is
-// the dispatch order.  Blocks past the last full 8*s span keep their index.
-__device__ __forceinline__ uint32_t xcd_chunk_remap(uint32_t b, uint32_t nb, uint32_t s) {
-  if (s <= 1) return b;
-  const uint32_t span = kNumXcd * s;
-  if (b >= (nb / span) * span) return b;
-  const uint32_t i = b / kNumXcd, x = b % kNumXcd;
-  return (i / s) * span + x * s + (i % s);
-}
+// Block order: xcd_chunk_remap / sweep_block (hspmv_internal.h), shared with
+// the host.
 
 __device__ __forceinline__ unsigned long long bits_from(int i) {
   return i >= 64 ? 0ull : (~0ull << i);
@@ -575,7 +561,7 @@ __device__ __forceinline__ void stage_xdict(T *xs, const T *__restrict__ x, cons
 // kXWin entries gather from an LDS copy of it.
 template <typename T, bool NT, int U, bool PF, int C16, bool XW, bool XD, int W = 4, bool PAD = false>
 __global__ __launch_bounds__(W * 64) void hspmv_csr_stream(
-    int32_t m, int32_t long_t, int32_t serial_max, uint32_t xcd_chunk, int32_t groups, int32_t y_nt,
+    int32_t m, int32_t long_t, int32_t serial_max, uint32_t blk_order, int32_t groups, int32_t y_nt,
     int32_t carry,
     const int32_t *__restrict__ rp, ColSrc cs, const int2 *__restrict__ xwin, XDict xd,
     const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y) {
@@ -585,7 +571,7 @@ __global__ __launch_bounds__(W * 64) void hspmv_csr_stream(
   extern __shared__ __attribute__((aligned(16))) unsigned char xdyn[];  // XD: the block's xs
   const int wid = threadIdx.x >> 6;
   const int lane = threadIdx.x & (kWave - 1);
-  const int64_t blk = xcd_chunk_remap(blockIdx.x, gridDim.x, xcd_chunk);
+  const int64_t blk = sweep_block(blockIdx.x, gridDim.x, blk_order);
   // XD (groups == 1): the block's 256 rows share one staged dictionary; the
   // only block barrier of the kernel is at the end of the staging.
   if constexpr (XD) stage_xdict<T, 256>(reinterpret_cast<T *>(xdyn), x, xd, blk, threadIdx.x);
@@ -636,7 +622,7 @@ __global__ __launch_bounds__(W * 64) void hspmv_csr_stream(
 
 template <typename T, bool NT, int U, bool PF, int C16, int W, bool XW, bool XD>
 __global__ __launch_bounds__(W * 64) void hspmv_csr3(
-    int32_t n_tasks, int32_t long_t, int32_t serial_max, uint32_t xcd_chunk, int32_t y_nt, int32_t carry,
+    int32_t n_tasks, int32_t long_t, int32_t serial_max, uint32_t blk_order, int32_t y_nt, int32_t carry,
     int32_t align,
     const int32_t *__restrict__ task_start, const int2 *__restrict__ xwin, XDict xd,
     const int32_t *__restrict__ rp, ColSrc cs, const T *__restrict__ val,
@@ -646,7 +632,7 @@ __global__ __launch_bounds__(W * 64) void hspmv_csr3(
   extern __shared__ __attribute__((aligned(16))) unsigned char xdyn[];  // XD: the block's xs
   const int wid = threadIdx.x >> 6;
   const int lane = threadIdx.x & (kWave - 1);
-  const int64_t blk = xcd_chunk_remap(blockIdx.x, gridDim.x, xcd_chunk);
+  const int64_t blk = sweep_block(blockIdx.x, gridDim.x, blk_order);
 #if (HSPMV_DIAG & 512)
   unsigned long long *bt = blk < kTraceWaves ? g_trace + blk * kTraceSlots : nullptr;
   if (bt && threadIdx.x == 0) {
@@ -883,7 +869,7 @@ __device__ __forceinline__ T slice_consume(T acc, const SliceBatch<T, B> &q, con
 // columns in batches of B, the next batch's loads issued before the current
 // one is consumed.  LDS: the dictionary alone.
 template <typename T, bool NT, int B, int PB>
-__global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t xcd_chunk, int32_t y_nt,
+__global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t blk_order, int32_t y_nt,
                                                     Slices sl, XDict xd, const T *__restrict__ val,
                                                     const T *__restrict__ x, T *__restrict__ y) {
   static_assert(B % 4 == 0 && B >= 4, "batches hold whole position groups");
@@ -891,7 +877,7 @@ __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t x
   extern __shared__ __attribute__((aligned(16))) unsigned char xdyn[];
   const int wid = threadIdx.x >> 6;
   const int lane = threadIdx.x & (kWave - 1);
-  const int64_t blk = xcd_chunk_remap(blockIdx.x, gridDim.x, xcd_chunk);
+  const int64_t blk = sweep_block(blockIdx.x, gridDim.x, blk_order);
   const int64_t t = blk * 4 + wid;
   int32_t off = 0, poff = 0, w = 0, r0 = 0, nr = 0;
   if (t < n_slices) {  // wave-uniform
@@ -949,6 +935,12 @@ __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t x
 
 // ------------------------------------------------------------------ launchers
 
+// The kernels' block-order argument: the XCD chunk, and the sweep direction
+// of this launch in the top bit (sweep_block).
+inline uint32_t block_order(const LaunchPlan &p) {
+  return (uint32_t)p.xcd_chunk | (p.reverse ? kSweepReverse : 0u);
+}
+
 template <typename T, int PB>
 void launch_slices_pb(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st) {
   const Slices sl{dp.sl_desc, dp.sl_len, dp.sl_pos, dp.sl_ppre};
@@ -957,10 +949,10 @@ void launch_slices_pb(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, 
   const T *val = static_cast<const T *>(dp.sl_val);
   if (p.nontemporal)
     hipLaunchKernelGGL((hspmv_slices<T, true, HSPMV_SLICE_BATCH, PB>), dim3((unsigned)p.blocks), dim3(256), dyn,
-                       st, dp.n_slices, (uint32_t)p.xcd_chunk, (int32_t)p.y_nt, sl, xd, val, x, y);
+                       st, dp.n_slices, block_order(p), (int32_t)p.y_nt, sl, xd, val, x, y);
   else
     hipLaunchKernelGGL((hspmv_slices<T, false, HSPMV_SLICE_BATCH, PB>), dim3((unsigned)p.blocks), dim3(256), dyn,
-                       st, dp.n_slices, (uint32_t)p.xcd_chunk, (int32_t)p.y_nt, sl, xd, val, x, y);
+                       st, dp.n_slices, block_order(p), (int32_t)p.y_nt, sl, xd, val, x, y);
 }
 
 template <typename T>
@@ -992,7 +984,7 @@ void launch_rows_u(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, cons
     const int2 *xw = reinterpret_cast<const int2 *>(dp.xwin);
 #define HSPMV_STREAM(C, XW, XDX, W, PAD)                                                            \
   hipLaunchKernelGGL((hspmv_csr_stream<T, NT, U, PF, C, XW, XDX, W, PAD>), dim3((unsigned)p.blocks), \
-                     dim3(W * 64), dyn, st, A.m, dp.long_t, dp.serial_max, (uint32_t)p.xcd_chunk,       \
+                     dim3(W * 64), dyn, st, A.m, dp.long_t, dp.serial_max, block_order(p),       \
                      (int32_t)p.groups,                                                               \
                      (int32_t)p.y_nt, p.carry, A.row_ptr, cs, xw, xd, val, x, y)
     if constexpr (XD) {  // never padded (plan_launch: dictionaries are sized unpadded)
@@ -1026,7 +1018,7 @@ void launch_rows_u(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, cons
 #define HSPMV_CSR3(W, C, XW, X)                                                               \
   hipLaunchKernelGGL((hspmv_csr3<T, NT, U, PF, C, W, XW, X>), dim3((unsigned)p.blocks),      \
                      dim3(W * 64), dyn, st, dp.n_tasks, dp.long_t, dp.serial_max,             \
-                     (uint32_t)p.xcd_chunk,                                                   \
+                     block_order(p),                                                   \
                      (int32_t)p.y_nt, p.carry, dp.task_align, dp.task_start, xw, xd, A.row_ptr, cs, \
                      val, x, y)
   if constexpr (XD) {  // packed tasks only (4 or 8 per block)

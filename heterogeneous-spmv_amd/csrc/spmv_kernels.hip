@@ -57,7 +57,10 @@
 //
 // Blocks are remapped so each of the 8 XCDs (private 4 MiB L2 each) gets a
 // contiguous range of row groups: neighbouring rows share x[] lines and the
-// edges of val/col lines, which then hit in one L2 instead of eight.
+// edges of val/col lines, which then hit in one L2 instead of eight.  Every
+// other SpMV of a handle whose matrix exceeds the Infinity Cache runs that
+// order mirrored, last block first (sweep_block, hspmv_internal.h;
+// hspmv_set_sweep), and so begins on the bytes the cache still holds.
 //
 // Build: hipcc --offload-arch=gfx950 -ffp-contract=off.  Contraction is off so
 // that only the explicit fma() calls (vector kernel, long rows) fuse.
@@ -327,8 +330,10 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
 
 }  // namespace
 
-hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, const LaunchPlan &plan,
-                       const void *x, void *y, hipStream_t stream) {
+hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, const LaunchPlan &fwd,
+                       const void *x, void *y, hipStream_t stream, bool reverse) {
+  LaunchPlan plan = fwd;
+  plan.reverse = reverse && (fwd.kernel == kStream || fwd.kernel == kCsr3);
   if (dtype == 1) {
     return plan.nontemporal
                ? launch_typed<double, true>(A, dp, plan, (const double *)x, (double *)y, stream)

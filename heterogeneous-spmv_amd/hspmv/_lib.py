@@ -124,7 +124,8 @@ class Info(C.Structure):
                 # since 1.1
                 ("csort_fixed_point", C.c_int32), ("serial_order", C.c_int32),
                 ("csort_part_begin", C.c_int64 * 4),
-                ("row_slices", C.c_int32), ("slice_pos_bits", C.c_int32)]
+                ("row_slices", C.c_int32), ("slice_pos_bits", C.c_int32),
+                ("sweep", C.c_int32), ("reserved1", C.c_int32)]
 
 
 CSR3_PLANS = {"auto": 0, "aligned": 1, "packed": 2, "ssr": 3}
@@ -133,6 +134,8 @@ DETERMINISTIC = {"any": 0, "ordered": 1, "reproducible": 2, "serial": 3}
 # hspmv_slices_plan's *why (HSPMV_SLICES_*)
 SLICES_WHY = {0: "ok", 1: "off", 2: "no_dict", 3: "shape", 4: "chunked", 5: "split_rows",
               6: "long_row", 7: "bytes", 8: "resident"}
+# hspmv_set_sweep's modes (HSPMV_SWEEP_*)
+SWEEP = {"auto": 0, "forward": 1, "alternate": 2}
 CSR3_PLAN_NAMES = {0: None, 1: "aligned", 2: "packed", 3: "ssr", 4: "row_groups"}
 
 
@@ -196,6 +199,8 @@ SIGNATURES = {
     "hspmv_y_device": (_P, [_H, C.c_int]),
     "hspmv_spmv": (C.c_int, [_H]),
     "hspmv_synchronize": (C.c_int, [_H]),
+    "hspmv_set_sweep": (C.c_int, [_H, C.c_int]),
+    "hspmv_block_order": (C.c_int, [C.c_int64, C.c_int32, C.c_int, _P]),
     "hspmv_run": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(Timing)]),
     "hspmv_get_y": (C.c_int, [_H, _P]),
     "hspmv_exchange": (C.c_int, [_H, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -479,6 +479,14 @@ class SpMV:
     def synchronize(self) -> None:
         check(lib().hspmv_synchronize(self._h), "hspmv_synchronize")
 
+    def set_sweep(self, mode: str) -> None:
+        """"auto" | "forward" | "alternate": whether the row kernel sweeps its
+        blocks in the opposite direction on every other SpMV (hspmv_set_sweep;
+        y is the same bits either way).  From the next call on."""
+        if mode not in _lib.SWEEP:
+            raise ValueError(f"sweep mode {mode!r} (one of {', '.join(_lib.SWEEP)})")
+        check(lib().hspmv_set_sweep(self._h, _lib.SWEEP[mode]), "hspmv_set_sweep")
+
     def run(self, warmup: int = 5, iters: int = 20) -> dict:
         t = _lib.Timing()
         check(lib().hspmv_run(self._h, int(warmup), int(iters), C.byref(t)), "hspmv_run")

@@ -79,7 +79,7 @@ def block_accesses(A, blk, runs, rows_per_block, val_bytes):
 
 
 def order_chunk(nb, chunk, nxcd=8):
-    """spmv_device.cuh xcd_chunk_remap: grid index -> block."""
+    """hspmv_internal.h xcd_chunk_remap: grid index -> block."""
     if chunk <= 1:
         return np.arange(nb, dtype=np.int32)
     span = nxcd * chunk

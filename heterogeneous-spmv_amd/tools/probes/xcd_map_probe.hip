@@ -1,6 +1,6 @@
 // xcd_map_probe.hip -- which XCD (and SE / CU) each workgroup of a launch
 // runs on.  The row kernels' block orders assume round-robin dispatch,
-// workgroup b on XCD b % 8 (spmv_device.cuh xcd_chunk_remap, the csort column
+// workgroup b on XCD b % 8 (hspmv_internal.h xcd_chunk_remap, the csort column
 // parts); this records the mapping a box actually uses, next to host.txt,
 // so a box whose dispatch differs can be told apart from a kernel change.
 //

@@ -49,7 +49,8 @@ extern "C" {
  * and 3 (HSPMV_DETERMINISTIC_SERIAL), hspmv_info.csort_fixed_point /
  * serial_order / csort_part_begin; hspmv_get_info frozen at the 1.0 layout
  * (HSPMV_INFO_SIZE_1_0).  Also in 1.1 (appended, nothing moved):
- * hspmv_options.row_slices, hspmv_info.row_slices, hspmv_slices_plan. */
+ * hspmv_options.row_slices, hspmv_info.row_slices, hspmv_slices_plan;
+ * hspmv_set_sweep, hspmv_block_order, hspmv_info.sweep. */
 
 /* ---------------------------------------------------------------- status */
 #define HSPMV_OK 0
@@ -212,6 +213,10 @@ typedef struct {
   int32_t slice_pos_bits;   /* bits per dictionary position in the row slices'
                                whole 8-slot groups (hspmv_slices_pack): 12 or
                                16; 0 without row slices (GPU 0)              */
+  int32_t sweep;            /* 1: the row kernel changes its sweep direction
+                               from one SpMV to the next (hspmv_set_sweep);
+                               0: first block to last on every call (GPU 0)  */
+  int32_t reserved1;
 } hspmv_info;
 
 typedef struct hspmv_handle hspmv_handle;
@@ -415,6 +420,35 @@ void *hspmv_y_device(hspmv_handle *h, int gpu);
 /* Enqueue ONE y = A*x on the handle's stream(s).  Asynchronous; the hot path. */
 int hspmv_spmv(hspmv_handle *h);
 int hspmv_synchronize(hspmv_handle *h);
+
+/* Sweep direction of the STREAM / CSR3 row kernel (the row-slice kernel
+ * included) from one SpMV of this handle to the next.  A matrix larger than
+ * the 256 MiB Infinity Cache that is swept first block to last on every call
+ * finds none of its bytes there: each line's reuse distance is the whole
+ * matrix.  With HSPMV_SWEEP_ALTERNATE every other hspmv_spmv (and every other
+ * timed or warm-up iteration of hspmv_run) runs the row kernel's workgroups
+ * last block to first, so a call starts on the bytes the previous call
+ * touched last.  y is bit-identical in both directions: a row's sum never
+ * leaves its workgroup, only the order of the workgroups changes.  Every
+ * shard of a call takes the same direction; the launches of a multi-launch
+ * SpMV keep their order, and the vector, column-sorted and split-row kernels
+ * always run forward.  HSPMV_SWEEP_AUTO (the default) alternates where the
+ * shard runs one row-kernel launch (no x slabs) over a matrix that does not
+ * fit the cache, and stays forward otherwise; HSPMV_SWEEP_FORWARD is first to
+ * last on every call.  Takes effect from the next call; other modes return
+ * HSPMV_E_INVALID.  hspmv_info.sweep reports the outcome.  A call captured
+ * into a HIP graph replays the direction it was captured with (no gain, no
+ * loss against FORWARD).  As before, one handle is not to be driven from two
+ * threads at once: the direction is state of the handle. */
+#define HSPMV_SWEEP_AUTO 0
+#define HSPMV_SWEEP_FORWARD 1
+#define HSPMV_SWEEP_ALTERNATE 2
+int hspmv_set_sweep(hspmv_handle *h, int mode);
+/* The row kernels' block order as the host sees it: order[b] = the logical
+ * block that grid index b runs among n_blocks, with xcd_chunk blocks per XCD
+ * turn (hspmv_info.xcd_remap; <= 1: dispatch order) and, reverse != 0, the
+ * mirrored sweep.  A bijection on [0, n_blocks); no device involved. */
+int hspmv_block_order(int64_t n_blocks, int32_t xcd_chunk, int reverse, int32_t *order);
 
 /* Reference timing protocol: warmup SpMVs, then iters timed SpMVs, each
  * bracketed by events + synchronize (hip/spmv-auto-mi100.cu:214-236). */
