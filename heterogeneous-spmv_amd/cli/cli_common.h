@@ -32,6 +32,12 @@
 //   --sweep forward|alternate   the row kernel's block sweep from one SpMV to
 //                       the next (hspmv_set_sweep; default: the library's
 //                       choice; y is the same bits either way)
+//   --rhs K             spmv-csr only: Y = A X for K right-hand sides (1..32) in one
+//                       pass over A (hspmv_mm_*), same protocol; column c of X
+//                       is the --x generator with seed SEED + c (ones: every
+//                       column ones); flops = 2 nnz K; prints "Rhs: K"; the
+//                       check runs per column; --dump-y writes the row-major
+//                       m x K array.  One GPU, the automatic kernel only.
 //   --dump-y PATH       write y as raw binary (dtype) for external checks
 //   --no-check          skip the serial CPU check
 #pragma once
@@ -60,6 +66,7 @@ struct Options {
   int deterministic = 0;  // hspmv_options.deterministic
   int sweep = HSPMV_SWEEP_AUTO;  // hspmv_set_sweep
   bool check = true;
+  int rhs = 0;  // > 0: the multi-vector operator with this many right-hand sides
   std::string dump_y;
   std::string params = "mi355x";
   bool bandk = true;  // spmv-csrk on a .csr: band-k reorder (the reference's CSRk_Graph)
@@ -123,6 +130,10 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
       if (!strcmp(v, "forward")) o.sweep = HSPMV_SWEEP_FORWARD;
       else if (!strcmp(v, "alternate")) o.sweep = HSPMV_SWEEP_ALTERNATE;
       else { fprintf(stderr, "bad --sweep %s\n", v); return false; }
+    } else if (a == "--rhs") {
+      const char *v = need("--rhs"); if (!v) return false;
+      o.rhs = atoi(v);
+      if (o.rhs < 1 || o.rhs > 32) { fprintf(stderr, "bad --rhs %s (1..32)\n", v); return false; }
     } else if (a == "--no-check") {
       o.check = false;
     } else if (a == "--dump-y") {
@@ -135,6 +146,14 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
       o.params = v;
     } else {
       fprintf(stderr, "unknown option %s\n", a.c_str());
+      return false;
+    }
+  }
+  if (o.rhs > 0) {  // the multi-vector operator: one device, one kernel, no planner options
+    if (o.gpus != 1) { fprintf(stderr, "--rhs runs on one GPU (not --gpus %d)\n", o.gpus); return false; }
+    if (o.kernel != HSPMV_KERNEL_AUTO) { fprintf(stderr, "--rhs has one kernel (only --kernel auto)\n"); return false; }
+    if (o.plan != HSPMV_CSR3_PLAN_AUTO || o.deterministic != 0 || o.sweep != HSPMV_SWEEP_AUTO) {
+      fprintf(stderr, "--rhs takes no --plan, --deterministic, --reproducible, --serial or --sweep\n");
       return false;
     }
   }
@@ -199,12 +218,102 @@ inline int die(const char *what) {
   return 1;
 }
 
+// --rhs K: the timed protocol through the multi-vector operator (hspmv_mm_*).
+inline int run_and_report_mm(const hspmv_csr_buf &A, int num_runs, const Options &o) {
+  hspmv_csr view = {A.m, A.n, A.nnz, A.row_ptr, A.col_idx, A.val, A.dtype};
+  const int K = o.rhs;
+  hspmv_options opt;
+  memset(&opt, 0, sizeof(opt));
+  opt.struct_size = sizeof(opt);
+  opt.flags = flags_of(o);
+  hspmv_mm *mm = nullptr;
+  if (hspmv_mm_create(&mm, &view, K, &opt) != HSPMV_OK) return die("hspmv_mm_create");
+  // row-major n x K: column c from the generator with seed + c
+  std::vector<double> X64((size_t)A.n * (size_t)K), col;
+  for (int c = 0; c < K; ++c) {
+    Options oc = o;
+    oc.seed = o.seed + (unsigned long long)c;
+    fill_x(oc, A.n, col);
+    for (int64_t i = 0; i < A.n; ++i) X64[(size_t)i * (size_t)K + (size_t)c] = col[(size_t)i];
+  }
+  std::vector<float> X32;
+  const void *xp = X64.data();
+  if (A.dtype == HSPMV_F32) {
+    X32.assign(X64.begin(), X64.end());
+    xp = X32.data();
+  }
+  if (hspmv_mm_set_x(mm, xp, K) != HSPMV_OK) return die("hspmv_mm_set_x");
+  hspmv_timing t;
+  if (hspmv_mm_run(mm, 5, num_runs, &t) != HSPMV_OK) return die("hspmv_mm_run");
+  hspmv_mm_info info;
+  if (hspmv_mm_get_info(mm, &info, sizeof(info)) != HSPMV_OK) return die("hspmv_mm_get_info");
+  printf("TimeMin: %lg\n", t.wall_min);
+  printf("TimeMax: %lg\n", t.wall_max);
+  printf("TimeAvg: %lg\n", t.wall_avg);
+  printf("KernelMin: %lg\n", t.t_min);
+  printf("KernelAvg: %lg\n", t.t_avg);
+  printf("GFLOPs: %lg\n", t.wall_min > 0 ? info.flops / t.wall_min * 1e-9 : 0.0);
+  printf("GBps: %lg\n", t.wall_min > 0 ? info.alg_bytes / t.wall_min * 1e-9 : 0.0);
+  printf("KernelGFLOPs: %lg\n", t.gflops);
+  printf("KernelGBps: %lg\n", t.gbps_alg);
+  printf("NumGPUs: %d\n", t.num_gpus);
+  printf("Kernel: spmm lanes_per_row=%d rows_per_wave=%d waves_per_block=%d blocks=%lld long_rows=%lld\n",
+         info.lanes_per_row, info.rows_per_wave, info.waves_per_block, (long long)info.blocks,
+         (long long)info.long_rows);
+  printf("Rhs: %d\n", K);
+  const size_t sv = A.dtype == HSPMV_F64 ? 8 : 4;
+  const size_t ny = (size_t)A.m * (size_t)K;
+  std::vector<char> Y(sv * (ny ? ny : 1));
+  if (hspmv_mm_get_y(mm, Y.data(), K) != HSPMV_OK) return die("hspmv_mm_get_y");
+  if (!o.dump_y.empty()) {
+    FILE *fp = fopen(o.dump_y.c_str(), "wb");
+    if (!fp || fwrite(Y.data(), sv, ny, fp) != ny) {
+      fprintf(stderr, "cannot write %s\n", o.dump_y.c_str());
+      return 1;
+    }
+    fclose(fp);
+  }
+  int rc = 0;
+  if (o.check) {  // the serial check per column; the report covers all columns
+    CheckResult all;
+    std::vector<double> x64((size_t)A.n), y64((size_t)A.m);
+    std::vector<float> x32((size_t)A.n), y32((size_t)A.m);
+    for (int c = 0; c < K; ++c) {
+      CheckResult r;
+      if (A.dtype == HSPMV_F64) {
+        for (int64_t i = 0; i < A.n; ++i) x64[(size_t)i] = X64[(size_t)i * (size_t)K + (size_t)c];
+        for (int64_t i = 0; i < A.m; ++i) y64[(size_t)i] = ((const double *)Y.data())[(size_t)i * (size_t)K + (size_t)c];
+        r = check_y<double>(A, (const double *)A.val, x64.data(), y64.data());
+      } else {
+        for (int64_t i = 0; i < A.n; ++i) x32[(size_t)i] = X32[(size_t)i * (size_t)K + (size_t)c];
+        for (int64_t i = 0; i < A.m; ++i) y32[(size_t)i] = ((const float *)Y.data())[(size_t)i * (size_t)K + (size_t)c];
+        r = check_y<float>(A, (const float *)A.val, x32.data(), y32.data());
+      }
+      all.wrong += r.wrong;
+      all.pass = all.pass && r.pass;
+      if (r.maxrel > all.maxrel) all.maxrel = r.maxrel;
+    }
+    printf("Number Wrong: %d \n", all.wrong);
+    printf("Check: %s maxrel=%.3e\n", all.pass ? "PASS" : "FAIL", all.maxrel);
+    rc = all.pass ? 0 : 2;
+  }
+  hspmv_mm_destroy(mm);
+  return rc;
+}
+
 // Runs the timed protocol on an already-read matrix and prints the report.
 // perm (optional, m entries): A is the band-k permutation of the file's
 // matrix, row i = file row perm[i]; x is generated in file order and
 // permuted, and a dumped y is put back in file order.
 inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, int num_runs,
                           const Options &o, const int32_t *perm = nullptr) {
+  if (o.rhs > 0) {
+    if ((maps && maps->n_ssr > 0) || perm) {
+      fprintf(stderr, "--rhs runs plain CSR (spmv-csr), not CSR-3 maps or a band-k order\n");
+      return 1;
+    }
+    return run_and_report_mm(A, num_runs, o);
+  }
   hspmv_csr view = {A.m, A.n, A.nnz, A.row_ptr, A.col_idx, A.val, A.dtype};
   hspmv_csr3_maps mv = {0, 0, nullptr, nullptr};
   if (maps && maps->n_ssr > 0) mv = {maps->n_ssr, maps->n_sr, maps->outer, maps->inner};

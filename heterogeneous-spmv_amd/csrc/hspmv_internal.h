@@ -5,6 +5,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "hspmv.h"
 
 namespace hspmv {
@@ -356,5 +358,42 @@ hipError_t launch_csort(const DevCsort &c, int dtype, const void *x, void *y, hi
 // vector, column-sorted and split-row kernels always run forward.
 hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, const LaunchPlan &plan,
                        const void *x, void *y, hipStream_t stream, bool reverse = false);
+
+// ---- multi-vector SpMM (spmm.hip, hspmv_mm.cpp): Y = A X, X row-major n x k
+constexpr int32_t kMmMaxRhs = 32;
+// Lanes one row takes: the smallest power of two >= k (k in [1, kMmMaxRhs]).
+inline int32_t mm_lanes_per_row(int32_t k) {
+  int32_t kp = 1;
+  while (kp < k) kp *= 2;
+  return kp;
+}
+// Grid of the row kernel: four waves per workgroup, 64 / kp rows per wave.
+inline int64_t mm_blocks(int64_t m, int32_t kp) {
+  const int64_t rows = 4 * (64 / kp);
+  return (m + rows - 1) / rows;
+}
+// Rows up to this many nonzeros carry omp_spmv's bits: the single-vector
+// kernels' serial bound of the dtype.
+inline int32_t mm_serial_max(int dtype) { return dtype == HSPMV_F64 ? kSerialMax : kSerialMaxF32; }
+// The ids of the rows over serial_max nonzeros, ascending (host only, no
+// device call: tools/spmm_plan_check.cpp runs it under the sanitizers).
+void mm_long_rows(const int32_t *row_ptr, int64_t m, int32_t serial_max, std::vector<int32_t> &rows);
+struct DevMM {
+  int32_t m = 0;
+  int64_t nnz = 0;
+  int32_t k = 1, lanes_per_row = 1;
+  int32_t serial_max = kSerialMax;
+  bool nontemporal = false;
+  const int32_t *row_ptr = nullptr;
+  const int32_t *col_idx = nullptr;
+  const void *val = nullptr;
+  const int32_t *long_row = nullptr;  // n_long row ids for the wave-per-row kernel
+  int32_t n_long = 0;
+};
+// Enqueues one Y = A X (the row kernel, then the long-row kernel when the
+// table is not empty).  Checks m, nnz, the leading dimensions and the grid
+// first: HSPMV_OK or an HSPMV_E_* code with the message set.
+int launch_spmm(const DevMM &d, int dtype, const void *X, int64_t ldx, void *Y, int64_t ldy,
+                hipStream_t stream);
 
 }  // namespace hspmv

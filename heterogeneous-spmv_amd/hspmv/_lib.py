@@ -128,6 +128,14 @@ class Info(C.Structure):
                 ("sweep", C.c_int32), ("reserved1", C.c_int32)]
 
 
+class MmInfo(C.Structure):
+    """hspmv_mm_info (include/hspmv.h): what a multi-vector operator runs."""
+    _fields_ = [("k", C.c_int32), ("lanes_per_row", C.c_int32), ("rows_per_wave", C.c_int32),
+                ("waves_per_block", C.c_int32), ("blocks", C.c_int64), ("long_rows", C.c_int64),
+                ("serial_max", C.c_int32), ("reserved0", C.c_int32), ("alg_bytes", C.c_double),
+                ("flops", C.c_double), ("device_bytes", C.c_int64)]
+
+
 CSR3_PLANS = {"auto": 0, "aligned": 1, "packed": 2, "ssr": 3}
 # hspmv_options.deterministic (HSPMV_DETERMINISTIC_*)
 DETERMINISTIC = {"any": 0, "ordered": 1, "reproducible": 2, "serial": 3}
@@ -207,6 +215,16 @@ SIGNATURES = {
     "hspmv_get_info": (C.c_int, [_H, C.POINTER(Info)]),
     "hspmv_get_info_sized": (C.c_int, [_H, C.POINTER(Info), C.c_uint32]),
     "hspmv_destroy": (None, [_H]),
+    "hspmv_mm_create": (C.c_int, [C.POINTER(_H), C.POINTER(Csr), C.c_int32, C.POINTER(Options)]),
+    "hspmv_mm_set_x": (C.c_int, [_H, _P, C.c_int64]),
+    "hspmv_mm_get_y": (C.c_int, [_H, _P, C.c_int64]),
+    "hspmv_mm_bind_x_device": (C.c_int, [_H, _P, C.c_int64]),
+    "hspmv_mm_bind_y_device": (C.c_int, [_H, _P, C.c_int64]),
+    "hspmv_mm_spmm": (C.c_int, [_H]),
+    "hspmv_mm_synchronize": (C.c_int, [_H]),
+    "hspmv_mm_run": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(Timing)]),
+    "hspmv_mm_get_info": (C.c_int, [_H, C.POINTER(MmInfo), C.c_uint32]),
+    "hspmv_mm_destroy": (None, [_H]),
     "hspmv_read_csr": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(CsrBuf)]),
     "hspmv_read_mtx": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(CsrBuf)]),
     "hspmv_rcm_reorder": (C.c_int, [C.POINTER(Csr), C.POINTER(CsrBuf), C.c_void_p]),

@@ -533,3 +533,116 @@ class SpMV:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class SpMM:
+    """Multi-vector operator Y = A X for ``k`` right-hand sides (1 <= k <= 32)
+    in one pass over A (a libhspmv ``hspmv_mm``).
+
+    X is row-major ``(n, k)`` -- what a contiguous numpy / torch array of that
+    shape is -- and Y row-major ``(m, k)``.  On every row of at most
+    ``info["serial_max"]`` nonzeros, column c of Y carries the bits
+    ``SpMV(A)(X[:, c])`` gives (omp_spmv's order); longer rows are summed in a
+    fixed order, bit-identical run to run.  One device; ``stream``: a
+    hipStream_t as an int (None: library-owned).
+    """
+
+    def __init__(self, A: CsrMatrix, k: int, *, device: int = 0, stream: Optional[int] = None,
+                 nontemporal: bool = False):
+        self._init_meta(A, k)
+        cs = A.c_struct()
+        self._create(cs, FLAG_NONTEMPORAL if nontemporal else 0, device, stream)
+
+    def _init_meta(self, A: CsrMatrix, k: int) -> None:
+        self._h = None
+        self.A = A
+        self.k = int(k)
+        self.dtype = A.val.dtype
+        if not 1 <= self.k <= 32:
+            raise ValueError(f"k = {k} right-hand sides (1 <= k <= 32)")
+
+    def _create(self, cs: "_lib.Csr", flags: int, device: int, stream: Optional[int]) -> None:
+        opt = _lib.make_options(flags, None, device=device, stream=stream)
+        h = C.c_void_p()
+        check(lib().hspmv_mm_create(C.byref(h), C.byref(cs), self.k, C.byref(opt)), "hspmv_mm_create")
+        self._h = h
+
+    @classmethod
+    def from_device(cls, csr_dev: "_lib.Csr", A_meta: CsrMatrix, k: int, *, device: int = 0,
+                    stream: Optional[int] = None, nontemporal: bool = False) -> "SpMM":
+        """Operator over caller-owned DEVICE arrays (HSPMV_FLAG_DEVICE_PTRS):
+        csr_dev holds device pointers; A_meta supplies m, n, dtype."""
+        self = cls.__new__(cls)
+        self._init_meta(A_meta, k)
+        self._create(csr_dev, FLAG_DEVICE_PTRS | (FLAG_NONTEMPORAL if nontemporal else 0), device, stream)
+        return self
+
+    # -- vectors
+    def _check_x(self, X) -> np.ndarray:
+        """X as a contiguous (n, k) array of the operator's dtype; ValueError
+        (before any library call) for another shape or a dtype that does not
+        cast to it."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape != (self.A.n, self.k):
+            raise ValueError(f"X has shape {X.shape}, expected (n, k) = ({self.A.n}, {self.k})")
+        if not np.can_cast(X.dtype, self.dtype, casting="same_kind"):
+            raise ValueError(f"X has dtype {X.dtype}, which does not cast to {np.dtype(self.dtype)}")
+        return np.ascontiguousarray(X, dtype=self.dtype)
+
+    def set_x(self, X: np.ndarray) -> None:
+        X = self._check_x(X)
+        check(lib().hspmv_mm_set_x(self._h, _ptr(X), self.k), "hspmv_mm_set_x")
+
+    def bind_x_device(self, ptr: Optional[int], ldx: Optional[int] = None) -> None:
+        """X on the device: n rows of ldx elements (default k); None: the operator's own buffer."""
+        check(lib().hspmv_mm_bind_x_device(self._h, ptr, self.k if ldx is None else int(ldx)),
+              "hspmv_mm_bind_x_device")
+
+    def bind_y_device(self, ptr: Optional[int], ldy: Optional[int] = None) -> None:
+        check(lib().hspmv_mm_bind_y_device(self._h, ptr, self.k if ldy is None else int(ldy)),
+              "hspmv_mm_bind_y_device")
+
+    # -- compute
+    def spmm(self) -> None:
+        check(lib().hspmv_mm_spmm(self._h), "hspmv_mm_spmm")
+
+    def synchronize(self) -> None:
+        check(lib().hspmv_mm_synchronize(self._h), "hspmv_mm_synchronize")
+
+    def run(self, warmup: int = 5, iters: int = 20) -> dict:
+        t = _lib.Timing()
+        check(lib().hspmv_mm_run(self._h, int(warmup), int(iters), C.byref(t)), "hspmv_mm_run")
+        return {f: getattr(t, f) for f, _ in _lib.Timing._fields_}
+
+    def get_y(self) -> np.ndarray:
+        Y = np.empty((self.A.m, self.k), dtype=self.dtype)
+        check(lib().hspmv_mm_get_y(self._h, _ptr(Y), self.k), "hspmv_mm_get_y")
+        return Y
+
+    def __call__(self, X: np.ndarray) -> np.ndarray:
+        self.set_x(X)
+        self.spmm()
+        return self.get_y()
+
+    @property
+    def info(self) -> dict:
+        i = _lib.MmInfo()
+        check(lib().hspmv_mm_get_info(self._h, C.byref(i), C.sizeof(i)), "hspmv_mm_get_info")
+        return {f: getattr(i, f) for f, _ in _lib.MmInfo._fields_}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().hspmv_mm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -50,7 +50,8 @@ extern "C" {
  * serial_order / csort_part_begin; hspmv_get_info frozen at the 1.0 layout
  * (HSPMV_INFO_SIZE_1_0).  Also in 1.1 (appended, nothing moved):
  * hspmv_options.row_slices, hspmv_info.row_slices, hspmv_slices_plan;
- * hspmv_set_sweep, hspmv_block_order, hspmv_info.sweep. */
+ * hspmv_set_sweep, hspmv_block_order, hspmv_info.sweep; the multi-vector
+ * operator hspmv_mm_* (hspmv_mm, hspmv_mm_info). */
 
 /* ---------------------------------------------------------------- status */
 #define HSPMV_OK 0
@@ -472,6 +473,70 @@ int hspmv_get_info(hspmv_handle *h, hspmv_info *out);
  * the header you were built against. */
 int hspmv_get_info_sized(hspmv_handle *h, hspmv_info *out, uint32_t out_size);
 void hspmv_destroy(hspmv_handle *h);
+
+/* ---------------------------------------------------------------- SpMM */
+/* Multi-vector product Y = A X for k right-hand sides (1 <= k <= 32) in one
+ * pass over A: what block CG / block GMRES, eigensolvers with a block of
+ * vectors and many-load-case solves call instead of k SpMVs, each of which
+ * streams the whole matrix from HBM.  A second, small operator beside
+ * hspmv_handle: it keeps A as plain CSR (a single-vector handle's formats --
+ * 16-bit columns, dictionaries, row slices -- are built for one vector).
+ *
+ * X is ROW-MAJOR n x k with leading dimension ldx >= k (the k values of one
+ * row contiguous; element (i, c) at X[i * ldx + c]), Y row-major m x k with
+ * ldy >= k: a contiguous torch / numpy array of shape (n, k) binds as it is,
+ * ldx = k.  Columns c >= k of a padded X are never read and those of Y never
+ * written.
+ *
+ * Order contract: for every row of at most serial_max nonzeros (40 in fp64,
+ * 56 in fp32; hspmv_mm_info.serial_max) column c of Y is bit for bit what
+ * omp_spmv (spmv-csr/spmv.c:92-114) gives for x = X[:, c] -- products rounded,
+ * added left to right from 0, no fma -- which is also what the ordered kernels
+ * behind hspmv_spmv give on those rows.  Longer rows are summed by one wave per
+ * row in a fixed order: bit-identical run to run, within the usual tolerance
+ * of omp_spmv.  Rows over 4096 nonzeros stay on one wave in this version.
+ *
+ * From hspmv_options only struct_size, flags (HSPMV_FLAG_DEVICE_PTRS and
+ * HSPMV_FLAG_NONTEMPORAL; the kernel code must be HSPMV_KERNEL_AUTO), device
+ * and stream are read; every other field is ignored (n_devices > 1 is
+ * refused).  NULL: defaults on device 0.
+ *
+ * Out of scope: multi-GPU shards, k > 32, CSR-3 maps, x dictionaries or row
+ * slices for X, column-major X, alpha / beta scaling, splitting rows over
+ * 4096 nonzeros across workgroups. */
+typedef struct hspmv_mm hspmv_mm;
+typedef struct {
+  int32_t k, lanes_per_row, rows_per_wave, waves_per_block;
+  int64_t blocks;          /* main-kernel grid */
+  int64_t long_rows;       /* rows run by the wave-per-row kernel */
+  int32_t serial_max;      /* rows up to this length carry omp_spmv's bits */
+  int32_t reserved0;
+  double alg_bytes;        /* nnz*(sv+4) + (m+1)*4 + (x_entries + m)*k*sv */
+  double flops;            /* 2 * nnz * k */
+  int64_t device_bytes;
+} hspmv_mm_info;
+
+int hspmv_mm_create(hspmv_mm **mm, const hspmv_csr *A, int32_t k, const hspmv_options *opt);
+/* X (row-major n x k, ldx >= k) from host memory into the operator's own
+ * buffer, which becomes the X in use. */
+int hspmv_mm_set_x(hspmv_mm *mm, const void *X_host, int64_t ldx);
+/* Y in use (own or bound) -> host, row-major m x k with ldy >= k; padding
+ * columns of Y_host are left as they are.  Synchronizes the stream. */
+int hspmv_mm_get_y(hspmv_mm *mm, void *Y_host, int64_t ldy);
+/* Bind caller-owned device arrays on the operator's device (X: n rows of ldx
+ * elements, Y: m rows of ldy).  NULL restores the operator's own buffer
+ * (leading dimension k). */
+int hspmv_mm_bind_x_device(hspmv_mm *mm, const void *X_dev, int64_t ldx);
+int hspmv_mm_bind_y_device(hspmv_mm *mm, void *Y_dev, int64_t ldy);
+/* Enqueue ONE Y = A X on the operator's stream.  Asynchronous. */
+int hspmv_mm_spmm(hspmv_mm *mm);
+int hspmv_mm_synchronize(hspmv_mm *mm);
+/* The timing protocol of hspmv_run; gflops = 2 nnz k / t_min, gbps_alg =
+ * hspmv_mm_info.alg_bytes / t_min. */
+int hspmv_mm_run(hspmv_mm *mm, int warmup, int iters, hspmv_timing *out);
+/* Fills min(out_size, sizeof(hspmv_mm_info)) bytes. */
+int hspmv_mm_get_info(hspmv_mm *mm, hspmv_mm_info *out, uint32_t out_size);
+void hspmv_mm_destroy(hspmv_mm *mm);
 
 /* ---------------------------------------------------------------- formats */
 /* Text .csr reader (spmv-csr/spmv.c:11-57 layout; index base auto-detected
