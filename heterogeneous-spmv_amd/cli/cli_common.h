@@ -16,6 +16,13 @@
 // Options (after the positional arguments):
 //   --gpus N            row-range partition over N GPUs (RCCL x-bcast / y-gather)
 //   --dtype f32|f64     value type (default f64; f32 = the reference's type)
+//   --vector-dtype f32|f64   type of x, y, the products and the sums (default:
+//                       --dtype).  f64 with --dtype f32 is the mixed handle
+//                       (hspmv_create_mixed): the file is read as fp32 and
+//                       streamed as fp32, the check is the fp64 host sum of
+//                       the widened values and --dump-y writes fp64; any
+//                       other unequal pair prints the library's message and
+//                       exits non-zero
 //   --x ones|rand:SEED  input vector (default ones, as the reference)
 //   --kernel auto|stream|vector[:L]|csr3|csort
 //   --nt                non-temporal loads of the matrix streams
@@ -57,6 +64,7 @@ namespace cli {
 struct Options {
   int gpus = 1;
   int dtype = HSPMV_F64;
+  int vector_dtype = -1;  // < 0: dtype
   bool x_rand = false;
   unsigned long long seed = 42;
   unsigned kernel = HSPMV_KERNEL_AUTO;
@@ -96,6 +104,11 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
       if (!strcmp(v, "f32")) o.dtype = HSPMV_F32;
       else if (!strcmp(v, "f64")) o.dtype = HSPMV_F64;
       else { fprintf(stderr, "bad --dtype %s\n", v); return false; }
+    } else if (a == "--vector-dtype") {
+      const char *v = need("--vector-dtype"); if (!v) return false;
+      if (!strcmp(v, "f32")) o.vector_dtype = HSPMV_F32;
+      else if (!strcmp(v, "f64")) o.vector_dtype = HSPMV_F64;
+      else { fprintf(stderr, "bad --vector-dtype %s\n", v); return false; }
     } else if (a == "--x") {
       const char *v = need("--x"); if (!v) return false;
       if (!strcmp(v, "ones")) o.x_rand = false;
@@ -312,6 +325,10 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
       fprintf(stderr, "--rhs runs plain CSR (spmv-csr), not CSR-3 maps or a band-k order\n");
       return 1;
     }
+    if (o.vector_dtype >= 0 && o.vector_dtype != A.dtype) {
+      fprintf(stderr, "--rhs has one dtype (no --vector-dtype other than --dtype)\n");
+      return 1;
+    }
     return run_and_report_mm(A, num_runs, o);
   }
   hspmv_csr view = {A.m, A.n, A.nnz, A.row_ptr, A.col_idx, A.val, A.dtype};
@@ -331,8 +348,14 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
   opt.n_devices = gpus > 1 ? gpus : 0;
   opt.csr3_plan = o.plan;
   opt.deterministic = o.deterministic;
-  if (hspmv_create_ex(&h, &view, mv.n_ssr > 0 ? &mv : nullptr, &opt) != HSPMV_OK)
+  // vdt: the type of x and y (the values' unless --vector-dtype gives another)
+  const int vdt = o.vector_dtype >= 0 ? o.vector_dtype : A.dtype;
+  if (vdt != A.dtype) {
+    if (hspmv_create_mixed(&h, &view, mv.n_ssr > 0 ? &mv : nullptr, &opt, vdt) != HSPMV_OK)
+      return die("hspmv_create_mixed");
+  } else if (hspmv_create_ex(&h, &view, mv.n_ssr > 0 ? &mv : nullptr, &opt) != HSPMV_OK) {
     return die("hspmv_create_ex");
+  }
   if (o.sweep != HSPMV_SWEEP_AUTO && hspmv_set_sweep(h, o.sweep) != HSPMV_OK) return die("hspmv_set_sweep");
   std::vector<double> x64;
   fill_x(o, A.n, x64);
@@ -342,7 +365,7 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
   }
   std::vector<float> x32;
   const void *xp = x64.data();
-  if (A.dtype == HSPMV_F32) {
+  if (vdt == HSPMV_F32) {
     x32.assign(x64.begin(), x64.end());
     xp = x32.data();
   }
@@ -369,7 +392,7 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
          kname[(info.kernel >= 0 && info.kernel <= 4) ? info.kernel : 0], info.lanes,
          info.waves_per_block, (long long)info.blocks,
          pname[(info.csr3_plan >= 0 && info.csr3_plan <= 3) ? info.csr3_plan : 0], info.deterministic);
-  const size_t sv = A.dtype == HSPMV_F64 ? 8 : 4;
+  const size_t sv = vdt == HSPMV_F64 ? 8 : 4;
   std::vector<char> y(sv * (size_t)(A.m ? A.m : 1));
   if (hspmv_get_y(h, y.data()) != HSPMV_OK) return die("hspmv_get_y");
   if (!o.dump_y.empty()) {
@@ -387,9 +410,16 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
   }
   int rc = 0;
   if (o.check) {
-    CheckResult r = A.dtype == HSPMV_F64
-                        ? check_y<double>(A, (const double *)A.val, x64.data(), (const double *)y.data())
-                        : check_y<float>(A, (const float *)A.val, x32.data(), (const float *)y.data());
+    CheckResult r;
+    if (vdt == HSPMV_F64 && A.dtype == HSPMV_F32) {  // mixed: the fp64 sum of the widened values
+      const float *v32 = (const float *)A.val;
+      const std::vector<double> v64(v32, v32 + A.nnz);
+      r = check_y<double>(A, v64.data(), x64.data(), (const double *)y.data());
+    } else if (A.dtype == HSPMV_F64) {
+      r = check_y<double>(A, (const double *)A.val, x64.data(), (const double *)y.data());
+    } else {
+      r = check_y<float>(A, (const float *)A.val, x32.data(), (const float *)y.data());
+    }
     printf("Number Wrong: %d \n", r.wrong);
     printf("Check: %s maxrel=%.3e\n", r.pass ? "PASS" : "FAIL", r.maxrel);
     rc = r.pass ? 0 : 2;

@@ -21,23 +21,28 @@ int check_handle(hspmv_handle *h) {
   return HSPMV_OK;
 }
 
+// vec_dtype: the type of x, y, the products and the sums; < 0: A->dtype (the
+// stored values' type).  hspmv_create_mixed passes HSPMV_F64 over fp32 values.
 int create_single(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps, int device,
-                  void *stream, unsigned flags, const Tuning &tune) {
+                  void *stream, unsigned flags, const Tuning &tune, int vec_dtype = -1) {
   ContigScope contig(tune);
   if (int rc0 = check_deterministic(flags, tune)) return rc0;
   const bool devptrs = (flags & HSPMV_FLAG_DEVICE_PTRS) != 0;
   if (!A) return set_error(HSPMV_E_INVALID, "matrix is NULL");
+  if (vec_dtype < 0) vec_dtype = A->dtype;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
     return set_error(HSPMV_E_NODEV, "no HIP device available");
   if (device < 0 || device >= ndev)
     return set_error(HSPMV_E_NODEV, "device %d out of range (have %d)", device, ndev);
   std::unique_ptr<hspmv_handle> h(new hspmv_handle());
-  h->m = A->m; h->n = A->n; h->nnz = A->nnz; h->dtype = A->dtype; h->flags = flags;
+  h->m = A->m; h->n = A->n; h->nnz = A->nnz; h->dtype = vec_dtype; h->val_dtype = A->dtype; h->flags = flags;
   h->shards.resize(1);
   Shard &s = h->shards[0];
   s.device = device;
   s.tune = tune;
+  s.dtype = vec_dtype;
+  s.val_dtype = A->dtype;
   int rc;
   if (!devptrs) {
     if ((rc = validate_host_csr(A, true))) return rc;
@@ -88,24 +93,24 @@ int create_single(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *
     std::vector<char> vals(dtype_size(A->dtype) * (size_t)A->nnz);
     if (A->nnz) HIP_TRY(hipMemcpy(vals.data(), A->val, vals.size(), hipMemcpyDeviceToHost));
     // from here on the shard owns device memory: every error path frees it
-    if ((rc = build_row_tables(s, rp.data(), cols.data(), vals.data(), A->m, A->n, A->dtype, flags))) {
+    if ((rc = build_row_tables(s, rp.data(), cols.data(), vals.data(), A->m, A->n, flags))) {
       free_shard(s, true);
       return rc;
     }
     std::vector<char>().swap(vals);
     std::vector<int32_t>().swap(cols);
-    const size_t sv = dtype_size(A->dtype);
+    const size_t sv = dtype_size(vec_dtype);
     if ((rc = dev_alloc(&s.d_x, sv * (size_t)A->n, &s.bytes)) ||
         (rc = dev_alloc(&s.d_y, sv * (size_t)A->m, &s.bytes))) {
       free_shard(s, true);
       return rc;
     }
   }
-  if ((rc = finish_shard(s, A->dtype, flags, stream))) {
+  if ((rc = finish_shard(s, flags, stream))) {
     free_shard(s, h->borrowed);
     return rc;
   }
-  if (!devptrs && (rc = place_shard(s, A->n, A->dtype))) {
+  if (!devptrs && (rc = place_shard(s, A->n))) {
     free_shard(s, h->borrowed);
     return rc;
   }
@@ -123,7 +128,7 @@ bool shard_alternates(const hspmv_handle *h, const Shard &s) {
   if (h->sweep_mode == HSPMV_SWEEP_FORWARD || s.A.m == 0) return false;
   if (s.plan.kernel != kStream && s.plan.kernel != kCsr3) return false;
   if (h->sweep_mode == HSPMV_SWEEP_ALTERNATE) return true;
-  return s.dp.n_slabs == 0 && !mall_resident(s.A.m, h->n, s.A.nnz, h->dtype);
+  return s.dp.n_slabs == 0 && !mall_resident(s.A.m, h->n, s.A.nnz, h->dtype, h->val_dtype);
 }
 
 // The direction of the next SpMV on s; the caller flips h->sweep_phase once
@@ -201,6 +206,39 @@ int hspmv_create_ex(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps
                           flags, t);
   }
   return create_single(hp, A, maps, opt ? opt->device : 0, opt ? opt->stream : nullptr, flags, t);
+}
+
+int hspmv_create_mixed(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps,
+                       const hspmv_options *opt, int vector_dtype) {
+  clear_error();
+  if (!hp) return set_error(HSPMV_E_INVALID, "NULL handle pointer");
+  *hp = nullptr;
+  if (!A) return set_error(HSPMV_E_INVALID, "matrix is NULL");
+  // every refusal below comes before the first HIP call (no device needed)
+  int rc;
+  if ((rc = check_dtype_pair(A->dtype, vector_dtype))) return rc;
+  if (vector_dtype == A->dtype) return hspmv_create_ex(hp, A, maps, opt);
+  Tuning t;
+  if ((rc = tuning_from_options(opt, &t))) return rc;
+  tuning_from_env(&t);  // diagnostic builds only
+  const unsigned flags = opt ? opt->flags : 0u;
+  if (opt && (opt->n_devices > 1 || (opt->devices && opt->n_devices != 1)))
+    return set_error(HSPMV_E_INVALID, "a mixed handle (fp32 values, fp64 vectors) runs on one device: "
+                                      "n_devices = %d", opt->n_devices);
+  if (flag_kernel(flags) == kCsort || t.csort > 0)
+    return set_error(HSPMV_E_INVALID, "a mixed handle (fp32 values, fp64 vectors) has no column-sorted "
+                                      "kernel: HSPMV_KERNEL_CSORT / csort = 1 need equal dtypes");
+  const int device = opt ? (opt->devices ? opt->devices[0] : opt->device) : 0;
+  return create_single(hp, A, maps, device, opt ? opt->stream : nullptr, flags, t, vector_dtype);
+}
+
+int hspmv_get_dtypes(hspmv_handle *h, int *value_dtype, int *vector_dtype) {
+  clear_error();
+  int rc;
+  if ((rc = check_handle(h))) return rc;
+  if (value_dtype) *value_dtype = h->val_dtype;
+  if (vector_dtype) *vector_dtype = h->dtype;
+  return HSPMV_OK;
 }
 
 int hspmv_create(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps, int num_gpus,
@@ -292,7 +330,7 @@ int hspmv_spmv(hspmv_handle *h) {
   if (!h->x_set) return set_error(HSPMV_E_STATE, "x not set (hspmv_set_x / hspmv_bind_x_device)");
   for (auto &s : h->shards) {
     HIP_TRY(hipSetDevice(s.device));
-    hipError_t e = launch_spmv(s.A, s.dp, h->dtype, s.plan, s.x, s.y, s.stream, shard_reverse(h, s));
+    hipError_t e = launch_spmv(s.A, s.dp, h->dtype, h->val_dtype, s.plan, s.x, s.y, s.stream, shard_reverse(h, s));
     if (e != hipSuccess)
       return set_error(HSPMV_E_HIP, "SpMV launch on GPU %d failed: %s", s.device, hipGetErrorString(e));
   }
@@ -349,7 +387,7 @@ int hspmv_run(hspmv_handle *h, int warmup, int iters, hspmv_timing *out) {
     for (auto &s : h->shards) {
       HIP_TRY(hipSetDevice(s.device));
       HIP_TRY(hipEventRecord(s.ev0, s.stream));
-      hipError_t e = launch_spmv(s.A, s.dp, h->dtype, s.plan, s.x, s.y, s.stream, shard_reverse(h, s));
+      hipError_t e = launch_spmv(s.A, s.dp, h->dtype, h->val_dtype, s.plan, s.x, s.y, s.stream, shard_reverse(h, s));
       if (e != hipSuccess)
         return set_error(HSPMV_E_HIP, "SpMV launch failed: %s", hipGetErrorString(e));
       HIP_TRY(hipEventRecord(s.ev1, s.stream));
@@ -371,7 +409,7 @@ int hspmv_run(hspmv_handle *h, int warmup, int iters, hspmv_timing *out) {
   out->t_min = tmin; out->t_max = tmax; out->t_avg = tsum / iters;
   out->wall_min = wmin; out->wall_max = wmax; out->wall_avg = wsum / iters;
   out->gflops = tmin > 0 ? 2.0 * (double)h->nnz / tmin * 1e-9 : 0.0;
-  out->gbps_alg = tmin > 0 ? hspmv_alg_bytes(h->m, h->x_entries(), h->nnz, h->dtype, h->n_ssr, h->n_sr) / tmin * 1e-9 : 0.0;
+  out->gbps_alg = tmin > 0 ? alg_bytes_of(h->m, h->x_entries(), h->nnz, h->dtype, h->val_dtype, h->n_ssr, h->n_sr) / tmin * 1e-9 : 0.0;
   out->iters = iters;
   out->num_gpus = (int32_t)h->shards.size();
   return HSPMV_OK;
@@ -441,7 +479,7 @@ static int fill_info(hspmv_handle *h, hspmv_info *out) {
   out->num_gpus = (int32_t)h->shards.size();
   out->blocks = s.plan.blocks;
   out->x_entries = h->x_entries();
-  out->alg_bytes = hspmv_alg_bytes(h->m, out->x_entries, h->nnz, h->dtype, h->n_ssr, h->n_sr);
+  out->alg_bytes = alg_bytes_of(h->m, out->x_entries, h->nnz, h->dtype, h->val_dtype, h->n_ssr, h->n_sr);
   out->flops = 2.0 * (double)h->nnz;
   for (auto &sh : h->shards) out->device_bytes += sh.bytes;
   out->chunk_u = s.plan.u;

@@ -21,4 +21,12 @@ int validate_host_maps(const hspmv_csr3_maps *maps, int64_t m);
 
 inline size_t dtype_size(int dtype) { return dtype == HSPMV_F64 ? 8 : 4; }
 
+// hspmv_alg_bytes for values stored in val_dtype under vectors of dtype (the
+// mixed handles: 4 instead of 8 bytes per stored value).
+inline double alg_bytes_of(int64_t m, int64_t x_entries, int64_t nnz, int dtype, int val_dtype, int64_t n_ssr,
+                           int64_t n_sr) {
+  return hspmv_alg_bytes(m, x_entries, nnz, dtype, n_ssr, n_sr) -
+         (double)nnz * ((double)dtype_size(dtype) - (double)dtype_size(val_dtype));
+}
+
 }  // namespace hspmv

@@ -128,12 +128,14 @@ inline int32_t split_threshold(unsigned flags) {
 // Cache across back-to-back SpMVs (the planner's "resident" test).
 constexpr double kMallResident = 192.0 * 1024 * 1024;
 // The bytes one SpMV touches: values + 32-bit columns, row pointers + y, x.
-inline double footprint_bytes(int64_t m, int64_t n, int64_t nnz, int dtype) {
-  const double sv = dtype == HSPMV_F64 ? 8.0 : 4.0;
-  return (double)nnz * (sv + 4.0) + (double)m * (sv + 4.0) + (double)n * sv;
+// dtype: x and y; val_dtype: the stored values (a mixed handle's are fp32).
+inline double footprint_bytes(int64_t m, int64_t n, int64_t nnz, int dtype, int val_dtype) {
+  const double sx = dtype == HSPMV_F64 ? 8.0 : 4.0;
+  const double sv = val_dtype == HSPMV_F64 ? 8.0 : 4.0;
+  return (double)nnz * (sv + 4.0) + (double)m * (sx + 4.0) + (double)n * sx;
 }
-inline bool mall_resident(int64_t m, int64_t n, int64_t nnz, int dtype) {
-  return footprint_bytes(m, n, nnz, dtype) <= kMallResident;
+inline bool mall_resident(int64_t m, int64_t n, int64_t nnz, int dtype, int val_dtype) {
+  return footprint_bytes(m, n, nnz, dtype, val_dtype) <= kMallResident;
 }
 // The L2 of one XCD: gathers from an x (or a row group's slice of x) beyond
 // it miss L2.
@@ -340,7 +342,10 @@ inline int ssr_waves(double rows_per_ssr) {
 // hspmv_plan.cpp).
 // rows_per_ssr: mean rows per super-super-row (CSR-3 workgroup-per-SSR plan);
 // packed_tasks > 0: CSR-3 tasks packed from super-rows (4 per workgroup).
-LaunchPlan plan_launch(const DevCSR &A, int dtype, unsigned flags, double rows_per_ssr,
+// dtype: the vectors' (every launch-shape rule follows it: the LDS product
+// buffers hold it); val_dtype: the stored values' (the footprint, the matrix
+// streams' addressing).
+LaunchPlan plan_launch(const DevCSR &A, int dtype, int val_dtype, unsigned flags, double rows_per_ssr,
                        int64_t packed_tasks, const Tuning &t);
 
 // STREAM / CSR3 row kernels (stream_f32.hip / stream_f64.hip).
@@ -348,6 +353,10 @@ hipError_t launch_rows_f32(const DevCSR &A, const DevPlan &dp, const LaunchPlan 
                            const float *x, float *y, hipStream_t st);
 hipError_t launch_rows_f64(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
                            const double *x, double *y, hipStream_t st);
+// ... of a mixed handle: A.val / dp.sl_val / dp.slab_val hold float
+// (stream_f32v64.hip)
+hipError_t launch_rows_f32v64(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
+                              const double *x, double *y, hipStream_t st);
 
 // Column-sorted row-block kernel + its finishing pass (csort.hip).
 hipError_t launch_csort(const DevCsort &c, int dtype, const void *x, void *y, hipStream_t st);
@@ -356,7 +365,9 @@ hipError_t launch_csort(const DevCsort &c, int dtype, const void *x, void *y, hi
 // reverse: the STREAM / CSR3 / slice row kernel (each x-slab pass of it)
 // sweeps its blocks last to first; the launches keep their order, and the
 // vector, column-sorted and split-row kernels always run forward.
-hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, const LaunchPlan &plan,
+// dtype: x, y, products and sums; val_dtype: the stored values (equal, or
+// HSPMV_F32 under HSPMV_F64: the mixed handles).
+hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, int val_dtype, const LaunchPlan &plan,
                        const void *x, void *y, hipStream_t stream, bool reverse = false);
 
 // ---- multi-vector SpMM (spmm.hip, hspmv_mm.cpp): Y = A X, X row-major n x k

@@ -721,6 +721,25 @@ int hspmv_partition_rows(int64_t m, const int32_t *rp, const hspmv_csr3_maps *mp
   return HSPMV_OK;
 }
 
+int hspmv_values_fit_f32(const void *val, int64_t nnz, int dtype, int64_t *first_bad) {
+  clear_error();
+  if (nnz < 0 || (!val && nnz > 0)) return set_error(HSPMV_E_INVALID, "bad value array (nnz %lld)", (long long)nnz);
+  if (dtype != HSPMV_F32 && dtype != HSPMV_F64) return set_error(HSPMV_E_INVALID, "dtype %d unknown", dtype);
+  if (dtype == HSPMV_F32) return 1;
+  const double *v = static_cast<const double *>(val);
+  for (int64_t k = 0; k < nnz; ++k) {
+    // (bits, not ==: -0.0 and the NaN payloads count; a double that rounds,
+    // overflows or flushes on the way to float comes back another double)
+    const volatile float f = (float)v[k];
+    const double back = (double)f;
+    if (memcmp(&back, &v[k], sizeof(double)) != 0) {
+      if (first_bad) *first_bad = k;
+      return 0;
+    }
+  }
+  return 1;
+}
+
 double hspmv_alg_bytes(int64_t m, int64_t n, int64_t nnz, int dtype, int64_t n_ssr, int64_t n_sr) {
   const double sv = (double)dtype_size(dtype), si = 4.0;
   double b = (double)nnz * (sv + si) + (double)(m + 1) * si + (double)n * sv + (double)m * sv;

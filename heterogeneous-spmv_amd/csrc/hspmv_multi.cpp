@@ -30,7 +30,7 @@ int create_sharded(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps 
   if ((rc = validate_host_maps(maps, A->m))) return rc;
   const bool csr3 = maps && maps->n_ssr > 0;
   std::unique_ptr<hspmv_handle> h(new hspmv_handle());
-  h->m = A->m; h->n = A->n; h->nnz = A->nnz; h->dtype = A->dtype; h->flags = flags;
+  h->m = A->m; h->n = A->n; h->nnz = A->nnz; h->dtype = A->dtype; h->val_dtype = A->dtype; h->flags = flags;
   if (csr3) { h->n_ssr = maps->n_ssr; h->n_sr = maps->n_sr; }
   std::vector<int64_t> splits((size_t)num_gpus + 1);
   if ((rc = hspmv_partition_rows(A->m, A->row_ptr, csr3 ? maps : nullptr, num_gpus, splits.data())))
@@ -57,6 +57,7 @@ int create_sharded(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps 
     Shard &s = h->shards[p];
     s.device = devs[(size_t)p];
     s.tune = tune;
+    s.dtype = s.val_dtype = A->dtype;
     if ((rc = upload_shard(s, A, maps, splits[p], splits[p + 1], ssr_split[p], ssr_split[p + 1], 0,
                            flags))) {
       cleanup();
@@ -68,7 +69,7 @@ int create_sharded(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps 
       return rc;
     }
     s.d_y = (char *)s.d_yfull + sv * (size_t)(max_rows * p);
-    if ((rc = finish_shard(s, A->dtype, flags, nullptr))) {
+    if ((rc = finish_shard(s, flags, nullptr))) {
       cleanup();
       return rc;
     }

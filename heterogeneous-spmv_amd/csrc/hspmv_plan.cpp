@@ -43,7 +43,7 @@ int pick_u(double nnz_per_pass, int dtype, bool slabs) {
 
 }  // namespace
 
-LaunchPlan plan_launch(const DevCSR &A, int dtype, unsigned flags, double rows_per_ssr,
+LaunchPlan plan_launch(const DevCSR &A, int dtype, int val_dtype, unsigned flags, double rows_per_ssr,
                        int64_t packed_tasks, const Tuning &t) {
   LaunchPlan p;
   const unsigned k = flag_kernel(flags);
@@ -59,8 +59,10 @@ LaunchPlan plan_launch(const DevCSR &A, int dtype, unsigned flags, double rows_p
   // streams 3-8 % faster (profiles/r01_sweep2-4: C2 full remap 15.6 vs
   // 16.9 us; C3 132 vs 128, C4 70.6 vs 65.4).  Chunked orders in between:
   // xcd_chunk_remap in spmv_device.cuh.
+  // sv: bytes of an x entry; sval: of a stored value (a mixed handle: 8 and 4)
   const double sv = dtype == HSPMV_F64 ? 8.0 : 4.0;
-  const bool resident = mall_resident(A.m, A.n, A.nnz, dtype);
+  const double sval = val_dtype == HSPMV_F64 ? 8.0 : 4.0;
+  const bool resident = mall_resident(A.m, A.n, A.nnz, dtype, val_dtype);
   bool full = false;
   int32_t chunk = 1;
   if (flag_xcd_chunk(flags))
@@ -140,7 +142,7 @@ LaunchPlan plan_launch(const DevCSR &A, int dtype, unsigned flags, double rows_p
   // could stream 4 GiB, would wrap.  Such matrices take a kernel that
   // indexes through pointers: csort when it was built, else VECTOR.
   const double max_run_bytes =
-      (flags & HSPMV_FLAG_NO_SPLIT) ? (double)A.nnz * (sv > 4.0 ? sv : 4.0) : 64.0 * kLongRow * sv;
+      (flags & HSPMV_FLAG_NO_SPLIT) ? (double)A.nnz * (sval > 4.0 ? sval : 4.0) : 64.0 * kLongRow * sval;
   if ((p.kernel == kStream || p.kernel == kCsr3) &&
       ((double)A.n * sv > 4294967295.0 || max_run_bytes > 4294967295.0))
     p.kernel = A.has_csort ? kCsort : kVector;

@@ -47,6 +47,10 @@ struct Shard {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   int64_t row0 = 0;  // first global row
+  // dtype: x, y, the products and the sums; val_dtype: the stored values
+  // (A.val, the slab and slice copies).  Equal, or HSPMV_F32 under HSPMV_F64
+  // (hspmv_create_mixed).  Set before upload_shard / build_row_tables.
+  int dtype = HSPMV_F64, val_dtype = HSPMV_F64;
   DevCSR A;          // device view (rows rebased to 0)
   LaunchPlan plan;
   double mean_rows_per_ssr = 0.0;
@@ -128,7 +132,8 @@ struct Shard {
 struct hspmv_handle {
   std::vector<hspmv::Shard> shards;
   int64_t m = 0, n = 0, nnz = 0;
-  int dtype = HSPMV_F64;
+  int dtype = HSPMV_F64;      // x, y, products and sums
+  int val_dtype = HSPMV_F64;  // the stored matrix values (hspmv_create_mixed: HSPMV_F32 under HSPMV_F64)
   int64_t n_ssr = 0, n_sr = 0;
   unsigned flags = 0;
   bool x_set = false;
@@ -192,8 +197,8 @@ inline int upload(Shard &s, T **slot, const void *src, size_t bytes) {
 void free_shard(Shard &s, bool borrowed);
 int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_t r0, int64_t r1,
                  int64_t ssr0, int64_t ssr1, int64_t y_rows_alloc, unsigned flags);
-int finish_shard(Shard &s, int dtype, unsigned flags, void *stream);
-int place_shard(Shard &s, int64_t n, int dtype);
+int finish_shard(Shard &s, unsigned flags, void *stream);
+int place_shard(Shard &s, int64_t n);
 
 // ---- hspmv_tables.cpp
 int64_t count_distinct_cols(const int32_t *col, int64_t nnz, int64_t n);
@@ -203,16 +208,17 @@ void build_tasks(const int32_t *rp, int64_t m, const std::vector<int32_t> *inner
                  const std::vector<int32_t> *outer, unsigned flags, const Tuning &tune,
                  std::vector<int32_t> &ts, int *waves);
 bool irregular_gathers(const int32_t *rp, const int32_t *col, int64_t m, double sv);
+// (the vectors' and the values' dtypes: s.dtype, s.val_dtype)
 int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
-                     int64_t n, int dtype, unsigned flags);
-int build_plan_tables(Shard &s, int dtype, unsigned flags);
+                     int64_t n, unsigned flags);
+int build_plan_tables(Shard &s, unsigned flags);
 
 // ---- hspmv_xdict.cpp
 // Which row kernel the planner will pick for a shard with n_ssr
 // super-super-rows and (CSR-3) wave tasks.
 int kernel_for_tables(int64_t n_ssr, bool have_tasks, unsigned flags);
 int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n,
-                int dtype, unsigned flags, bool have_xwin);
+                unsigned flags, bool have_xwin);
 // The dictionaries of the workgroups whose rows are [bs[b], bs[b+1]).
 struct XdPlan {
   std::vector<int32_t> blk;  // nb + 1 record ranges
@@ -233,6 +239,9 @@ struct PlanShape {
   int W = 4, kern = kStream;
 };
 int plan_shape(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt, PlanShape &ps);
+// The pair a create / plan entry point was given: HSPMV_OK when vector_dtype
+// equals val_dtype or is HSPMV_F64 over HSPMV_F32 values, else E_INVALID.
+int check_dtype_pair(int val_dtype, int vector_dtype);
 int64_t xdict_cap_entries(int dtype, const Tuning &t);
 // slices: the workgroups' LDS is the dictionary alone (the slice kernel)
 bool plan_xdict_for(const int32_t *rp, const int32_t *col, int kern, int64_t m,
@@ -256,9 +265,11 @@ struct SlicePlan {
 std::vector<int32_t> slice_starts(int kern, int64_t m, const std::vector<int32_t> &tasks);
 // HSPMV_SLICES_OK when a handle with these options and rows takes the slice
 // format (dictionaries permitting), else the first rule it fails.
+// dtype: the vectors' (the serial bound); val_dtype: the stored values' (the
+// byte rule, the residence test; build_slices: the value groups).
 int slices_why(const Tuning &t, unsigned flags, int kern, int W, const int32_t *rp, int64_t m,
-               int64_t n, int dtype, const std::vector<int32_t> &starts, SliceCounts *out);
-void build_slices(const int32_t *rp, const uint16_t *pos, const void *val, int64_t m, int dtype,
+               int64_t n, int dtype, int val_dtype, const std::vector<int32_t> &starts, SliceCounts *out);
+void build_slices(const int32_t *rp, const uint16_t *pos, const void *val, int64_t m, int val_dtype,
                   const std::vector<int32_t> &starts, SlicePlan &P);
 int upload_slices(Shard &s, const SlicePlan &P);
 void drop_slices(Shard &s);
@@ -268,6 +279,7 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
                 int64_t n, int dtype, unsigned flags);
 
 // ---- hspmv_multi.cpp
+// (equal dtypes only: hspmv_create_mixed refuses more than one device)
 int create_sharded(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps,
                    const std::vector<int> &devs, unsigned flags, const Tuning &tune);
 int bcast_x(hspmv_handle *h);

@@ -91,7 +91,7 @@ void free_shard(Shard &s, bool borrowed) {
 // Uploads rows [r0, r1) of A (and the matching slice of the maps) to shard s.
 int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_t r0, int64_t r1,
                  int64_t ssr0, int64_t ssr1, int64_t y_rows_alloc, unsigned flags) {
-  const size_t sv = dtype_size(A->dtype);
+  const size_t sv = dtype_size(s.val_dtype), sx = dtype_size(s.dtype);  // stored values; x and y
   const int64_t m = r1 - r0;
   const int64_t k0 = A->row_ptr[r0], k1 = A->row_ptr[r1];
   const int64_t nnz = k1 - k0;
@@ -104,9 +104,9 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
   if ((rc = upload(s, &s.d_rp, rp.data(), 4 * (size_t)(m + 1)))) return rc;
   if ((rc = upload(s, &s.d_ci, A->col_idx + k0, 4 * (size_t)nnz))) return rc;
   if ((rc = upload(s, &s.d_val, (const char *)A->val + sv * k0, sv * (size_t)nnz))) return rc;
-  if ((rc = dev_alloc(&s.d_x, sv * (size_t)A->n, &s.bytes))) return rc;
+  if ((rc = dev_alloc(&s.d_x, sx * (size_t)A->n, &s.bytes))) return rc;
   if (y_rows_alloc > 0) {
-    if ((rc = dev_alloc(&s.d_y, sv * (size_t)y_rows_alloc, &s.bytes))) return rc;
+    if ((rc = dev_alloc(&s.d_y, sx * (size_t)y_rows_alloc, &s.bytes))) return rc;
   }
   s.x_entries = count_distinct_cols(A->col_idx + k0, nnz, A->n);
   s.A.m = (int32_t)m;
@@ -133,11 +133,10 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
     s.A.inner = s.d_inner;
     s.mean_rows_per_ssr = nssr ? (double)m / (double)nssr : 0.0;
   }
-  return build_row_tables(s, rp.data(), A->col_idx + k0, (const char *)A->val + sv * k0, m, A->n,
-                          A->dtype, flags);
+  return build_row_tables(s, rp.data(), A->col_idx + k0, (const char *)A->val + sv * k0, m, A->n, flags);
 }
 
-int finish_shard(Shard &s, int dtype, unsigned flags, void *stream) {
+int finish_shard(Shard &s, unsigned flags, void *stream) {
   HIP_TRY(hipSetDevice(s.device));
   if (stream) {
     s.stream = (hipStream_t)stream;
@@ -151,9 +150,9 @@ int finish_shard(Shard &s, int dtype, unsigned flags, void *stream) {
   // CSR-3 block size from the mean rows per super-super-row (sizing on the
   // 90th percentile doubled C3's waves for a 7-12 % loss, r01_ab_csr3_tasks)
   const double ssr_rows = s.mean_rows_per_ssr;
-  s.plan = plan_launch(s.A, dtype, flags, ssr_rows,
+  s.plan = plan_launch(s.A, s.dtype, s.val_dtype, flags, ssr_rows,
                        s.h_tasks.empty() ? 0 : (int64_t)s.h_tasks.size() - 1, s.tune);
-  int rc = build_plan_tables(s, dtype, flags);
+  int rc = build_plan_tables(s, flags);
   if (rc) return rc;
   s.x = s.d_x;
   s.y = s.d_y;
@@ -165,14 +164,14 @@ int finish_shard(Shard &s, int dtype, unsigned flags, void *stream) {
 
 // Mean SpMV time (us) of the shard's current arrays: 2 warm-up launches, then
 // the best of 3 event-timed runs of 5 launches.  < 0 on a launch error.
-static double time_shard(Shard &s, int dtype) {
+static double time_shard(Shard &s) {
   for (int i = 0; i < 2; ++i)
-    if (launch_spmv(s.A, s.dp, dtype, s.plan, s.x, s.y, s.stream) != hipSuccess) return -1.0;
+    if (launch_spmv(s.A, s.dp, s.dtype, s.val_dtype, s.plan, s.x, s.y, s.stream) != hipSuccess) return -1.0;
   double best = 1e30;
   for (int r = 0; r < 3; ++r) {
     if (hipEventRecord(s.ev0, s.stream) != hipSuccess) return -1.0;
     for (int i = 0; i < 5; ++i)
-      if (launch_spmv(s.A, s.dp, dtype, s.plan, s.x, s.y, s.stream) != hipSuccess) return -1.0;
+      if (launch_spmv(s.A, s.dp, s.dtype, s.val_dtype, s.plan, s.x, s.y, s.stream) != hipSuccess) return -1.0;
     float ms = 0.0f;
     if (hipEventRecord(s.ev1, s.stream) != hipSuccess || hipEventSynchronize(s.ev1) != hipSuccess ||
         hipEventElapsedTime(&ms, s.ev0, s.ev1) != hipSuccess)
@@ -202,16 +201,16 @@ static double time_shard(Shard &s, int dtype) {
 // arrays alone.
 static constexpr int kPlacementTrials = 0;
 
-int place_shard(Shard &s, int64_t n, int dtype) {
+int place_shard(Shard &s, int64_t n) {
   int trials = s.tune.placement_trials > 0 ? std::min(8, s.tune.placement_trials) : kPlacementTrials;
   if (trials <= 1 || (s.plan.kernel != kStream && s.plan.kernel != kCsr3) || s.A.m == 0) return HSPMV_OK;
   if (s.dp.sl_desc) return HSPMV_OK;  // row slices: the trial sets copy the CSR-order streams
-  const size_t sv = dtype_size(dtype);
+  const size_t sv = dtype_size(s.dtype), sval = dtype_size(s.val_dtype);  // x and y; the stored values
   const int64_t m = s.A.m, nnz = s.A.nnz;
-  if (mall_resident(m, n, nnz, dtype)) return HSPMV_OK;  // served from the Infinity Cache: placement does not matter
+  if (mall_resident(m, n, nnz, s.dtype, s.val_dtype)) return HSPMV_OK;  // served from the Infinity Cache: placement does not matter
   struct Arr { void **slot; size_t bytes; };
   std::vector<Arr> arrs = {{(void **)&s.d_rp, 4 * (size_t)(m + 1)},
-                           {(void **)&s.d_val, sv * (size_t)nnz},
+                           {(void **)&s.d_val, sval * (size_t)nnz},
                            {(void **)&s.d_x, sv * (size_t)n},
                            {(void **)&s.d_y, sv * (size_t)m}};
   if (s.A.col16)
@@ -237,7 +236,7 @@ int place_shard(Shard &s, int64_t n, int dtype) {
   HIP_TRY(hipMemsetAsync(s.d_x, 0, sv * (size_t)n, s.stream));
   std::vector<std::vector<void *>> sets(1);
   for (auto &a : arrs) sets[0].push_back(*a.slot);
-  s.place_us.assign(1, time_shard(s, dtype));
+  s.place_us.assign(1, time_shard(s));
   if (s.place_us[0] < 0) return set_error(HSPMV_E_HIP, "placement trial: launch failed");
   int rc = HSPMV_OK;
   for (int k = 1; k < trials && rc == HSPMV_OK; ++k) {
@@ -259,7 +258,7 @@ int place_shard(Shard &s, int64_t n, int dtype) {
     }
     for (size_t i = 0; i < arrs.size(); ++i) *arrs[i].slot = set[i];
     point();
-    const double t = time_shard(s, dtype);
+    const double t = time_shard(s);
     sets.push_back(set);
     s.place_us.push_back(t);
     if (t < 0) rc = set_error(HSPMV_E_HIP, "placement trial: launch failed");

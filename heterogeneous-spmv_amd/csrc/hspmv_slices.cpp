@@ -47,10 +47,10 @@ namespace hspmv {
 //
 // Eligible (slices_why == HSPMV_SLICES_OK): dictionaries over the CSR3
 // aligned plan's tasks or STREAM's 64-row groups, no split rows, every row
-// within the dtype's serial bound, and the slice format's bytes per SpMV not
+// within the vector dtype's serial bound (a mixed handle: fp64's 40), and the slice format's bytes per SpMV not
 // above the CSR-order format's -- padded * (sv + 2) + m + 8 * (tasks + 1)
 // against nnz * (sv + 2) + 4 * (m + 1); the rest (run records, staged x, y) is
-// common.  A request for the chunked kernel's own knobs (HSPMV_U,
+// common; sv is the stored values' size (a mixed handle: 4).  A request for the chunked kernel's own knobs (HSPMV_U,
 // HSPMV_FLAG_PREFETCH, deterministic = 3) keeps that kernel.  Auto
 // (row_slices = 0) also asks for a matrix that streams from HBM, the
 // dictionaries' own rule.  The two rules about speed -- the bytes and the HBM
@@ -68,7 +68,7 @@ std::vector<int32_t> slice_starts(int kern, int64_t m, const std::vector<int32_t
 }
 
 int slices_why(const Tuning &t, unsigned flags, int kern, int W, const int32_t *rp, int64_t m,
-               int64_t n, int dtype, const std::vector<int32_t> &starts, SliceCounts *out) {
+               int64_t n, int dtype, int val_dtype, const std::vector<int32_t> &starts, SliceCounts *out) {
   SliceCounts c;
   c.n_desc = (int64_t)starts.size() - 1;
   for (int64_t s = 0; s < c.n_desc; ++s) {
@@ -95,13 +95,13 @@ int slices_why(const Tuning &t, unsigned flags, int kern, int W, const int32_t *
     return HSPMV_SLICES_CHUNKED;
   if (c.max_len > split_threshold(flags)) return HSPMV_SLICES_SPLIT_ROWS;
   if (c.max_len > (dtype == HSPMV_F32 ? kSerialMaxF32 : kSerialMax)) return HSPMV_SLICES_LONG_ROW;
-  const double sv = (double)dtype_size(dtype);
+  const double sv = (double)dtype_size(val_dtype);
   const double nnz = (double)rp[m];
   if (t.row_slices == 0 &&
       64.0 * (double)c.padded * (sv + 2.0) + (double)m + 8.0 * (double)(c.n_desc + 1) >
           nnz * (sv + 2.0) + 4.0 * (double)(m + 1))
     return HSPMV_SLICES_BYTES;
-  if (t.row_slices == 0 && mall_resident(m, n, rp[m], dtype)) return HSPMV_SLICES_RESIDENT;
+  if (t.row_slices == 0 && mall_resident(m, n, rp[m], dtype, val_dtype)) return HSPMV_SLICES_RESIDENT;
   return HSPMV_SLICES_OK;
 }
 
@@ -113,10 +113,10 @@ static inline size_t slot_at(size_t base, int32_t w, int32_t k, int i, int G) {
                 : base + (size_t)k * 64 + (size_t)i;
 }
 
-void build_slices(const int32_t *rp, const uint16_t *pos, const void *val, int64_t m, int dtype,
+void build_slices(const int32_t *rp, const uint16_t *pos, const void *val, int64_t m, int val_dtype,
                   const std::vector<int32_t> &starts, SlicePlan &P) {
   const int64_t nd = (int64_t)starts.size() - 1;
-  const size_t sv = dtype_size(dtype);
+  const size_t sv = dtype_size(val_dtype);
   const int G = 16 / (int)sv;
   P.desc.assign(2 * (size_t)(nd + 1), 0);
   int64_t pre = 0;
@@ -258,6 +258,14 @@ extern "C" {
 int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt,
                       int64_t *n_desc, int64_t *n_slices, int64_t *padded_entries, int32_t *why,
                       int32_t *desc, uint8_t *len, uint16_t *pos, void *val) {
+  // (a NULL or malformed A is refused by plan_shape, whatever the dtype read here)
+  return hspmv_slices_plan_vec(A, maps, opt, A ? A->dtype : HSPMV_F64, n_desc, n_slices, padded_entries, why,
+                               desc, len, pos, val);
+}
+
+int hspmv_slices_plan_vec(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt,
+                          int vector_dtype, int64_t *n_desc, int64_t *n_slices, int64_t *padded_entries,
+                          int32_t *why, int32_t *desc, uint8_t *len, uint16_t *pos, void *val) {
   clear_error();
   if (!n_desc || !n_slices || !padded_entries || !why) return set_error(HSPMV_E_INVALID, "NULL output");
   *n_desc = *n_slices = *padded_entries = 0;
@@ -265,13 +273,15 @@ int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hsp
   int rc;
   PlanShape ps;
   if ((rc = plan_shape(A, maps, opt, ps))) return rc;
+  if ((rc = check_dtype_pair(A->dtype, vector_dtype))) return rc;
+  const int vdt = vector_dtype;  // the dictionaries hold x entries; the slices' values stay A->dtype
   const Tuning &tune = ps.tune;
   const unsigned flags = ps.flags;
   std::vector<int32_t> &tasks = ps.tasks;
   const int W = ps.W, kern = ps.kern;
   if ((kern != kStream && kern != kCsr3) || A->m == 0) return HSPMV_OK;
   SliceCounts c;
-  *why = slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, A->dtype,
+  *why = slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, vdt, A->dtype,
                     slice_starts(kern, A->m, tasks), &c);
   *n_desc = c.n_desc;
   *n_slices = c.n_slices;
@@ -282,12 +292,12 @@ int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hsp
   const bool fill = desc || len || pos || val;
   int64_t cut = 0;
   if (!plan_xdict_for(A->row_ptr, A->col_idx, kern, A->m, tasks, W, long_t,
-                      xdict_cap_entries(A->dtype, tune), A->dtype, tune, true, fill, P, &cut)) {
+                      xdict_cap_entries(vdt, tune), vdt, tune, true, fill, P, &cut)) {
     *why = HSPMV_SLICES_NO_DICT;  // some block exceeds the LDS cap
     return HSPMV_OK;
   }
   const std::vector<int32_t> starts = slice_starts(kern, A->m, tasks);  // after the occupancy cuts
-  slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, A->dtype, starts, &c);
+  slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, vdt, A->dtype, starts, &c);
   *n_desc = c.n_desc;
   if (!fill) return HSPMV_OK;
   SlicePlan S;

@@ -38,7 +38,7 @@ int build_col16(Shard &s, const int32_t *col, int64_t nnz, int64_t m, int64_t n,
   *used = false;
   if (nnz == 0) return HSPMV_OK;
   const bool forced = (flags & HSPMV_FLAG_COL16) != 0 && !(flags & HSPMV_FLAG_NO_COL16);
-  if (!forced && mall_resident(m, n, nnz, dtype)) return HSPMV_OK;
+  if (!forced && mall_resident(m, n, nnz, dtype, s.val_dtype)) return HSPMV_OK;
   const int64_t B = int64_t(1) << kC16Shift;
   const int64_t nb = (nnz + B - 1) / B;
   std::vector<int32_t> base((size_t)nb + 1, 0);  // +1: kernels load bases in pairs
@@ -110,7 +110,7 @@ int build_col16g(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int
   const int64_t nnz = rp[m];
   if (mode < 0 || (flags & HSPMV_FLAG_NO_COL16) || nnz == 0) return HSPMV_OK;
   const bool forced = (flags & HSPMV_FLAG_COL16) != 0 || mode == 1;
-  if (!forced && !mall_resident(m, n, nnz, dtype)) return HSPMV_OK;
+  if (!forced && !mall_resident(m, n, nnz, dtype, s.val_dtype)) return HSPMV_OK;
   const int32_t long_t = split_threshold(flags);
   const int64_t ng = starts ? (int64_t)starts->size() - 1 : (m + 63) / 64;
   if (ng <= 0) return HSPMV_OK;
@@ -521,6 +521,9 @@ constexpr int kMaxSlabs = 32;
 
 int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
                  int64_t n, int dtype, unsigned flags) {
+  // sv: an x / y entry (the slab width, the passes' y traffic, the gathers);
+  // sval: a stored value (the matrix stream, the slab-major copy)
+  const double sval = (double)dtype_size(s.val_dtype);
   s.n_slabs = 0;
   const int forced = s.tune.x_slabs < 0 ? 0 : (s.tune.x_slabs > 0 ? s.tune.x_slabs : -1);  // -1 auto, 0 off, B slabs
   if (forced == 0 || !val || m == 0 || n == 0 || flag_kernel(flags) == kVector) return HSPMV_OK;
@@ -533,12 +536,12 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
   const int32_t long_t = split_threshold(flags);
   const int64_t W = (n + B - 1) / B;  // columns per slab
   if (forced < 0) {
-    if (mall_resident(m, n, nnz, dtype) || (double)n * sv <= kXcdL2Bytes) return HSPMV_OK;
+    if (mall_resident(m, n, nnz, dtype, s.val_dtype) || (double)n * sv <= kXcdL2Bytes) return HSPMV_OK;
     // the passes must pay: every extra one re-reads a row-pointer array and
     // y and rewrites y (at most a quarter of the matrix stream in total),
     // and each pass must stream millions of nonzeros (a launch is ~2-5 us)
     const double extra = (double)(B - 1) * (4.0 * (double)(m + 1) + 2.0 * sv * (double)m);
-    if (extra > 0.25 * (double)nnz * (sv + 4.0) || (double)nnz / B < 2.0e6) return HSPMV_OK;
+    if (extra > 0.25 * (double)nnz * (sval + 4.0) || (double)nnz / B < 2.0e6) return HSPMV_OK;
     if (!irregular_gathers(rp, col, m, sv)) return HSPMV_OK;
     // ... and only when the x a row group gathers from is wider than an
     // XCD's L2 (median 64-row group column span > 4 MiB of x): scattered but
@@ -574,7 +577,7 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
   }
   const int64_t snnz = base;  // in-kernel nonzeros (split rows excluded)
   std::vector<int32_t> scol((size_t)std::max<int64_t>(snnz, 1));
-  std::vector<char> sval((size_t)std::max<int64_t>(snnz, 1) * (size_t)sv);
+  std::vector<char> svals((size_t)std::max<int64_t>(snnz, 1) * (size_t)sval);
   parallel_ranges(m, 65536, [&](int64_t ra, int64_t rb, int) {
     for (int64_t r = ra; r < rb; ++r) {
       const int32_t k0 = rp[r], k1 = rp[r + 1];
@@ -584,8 +587,8 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
         const int32_t *p = srp.data() + (size_t)b * (size_t)(m + 1);
         for (int32_t o = p[r]; o < p[r + 1]; ++o, ++k) {
           scol[(size_t)o] = col[k];
-          memcpy(sval.data() + (size_t)o * (size_t)sv, (const char *)val + (size_t)k * (size_t)sv,
-                 (size_t)sv);
+          memcpy(svals.data() + (size_t)o * (size_t)sval, (const char *)val + (size_t)k * (size_t)sval,
+                 (size_t)sval);
         }
       }
     }
@@ -593,7 +596,7 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
   int rc;
   if ((rc = upload(s, &s.d_slab_rp, srp.data(), 4 * srp.size()))) return rc;
   if ((rc = upload(s, &s.d_slab_col, scol.data(), 4 * scol.size()))) return rc;
-  if ((rc = upload(s, &s.d_slab_val, sval.data(), sval.size()))) return rc;
+  if ((rc = upload(s, &s.d_slab_val, svals.data(), svals.size()))) return rc;
   s.n_slabs = B;
   return HSPMV_OK;
 }
@@ -623,7 +626,8 @@ void slab_kernel_rule(Shard &s, const int32_t *rp, int64_t m, unsigned flags) {
 // dictionaries) the 16-bit column offsets and the x windows of both row
 // kernels.
 int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
-                     int64_t n, int dtype, unsigned flags) {
+                     int64_t n, unsigned flags) {
+  const int dtype = s.dtype;  // the vectors'; the values': s.val_dtype
   // the typical serially summed row (median length of the rows of 1..40
   // nonzeros, spmv_device.cuh kSerialMax): the planner's LDS bank rule
   {
@@ -654,7 +658,9 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
     // an ordered or serial handle (deterministic = 1, 3) never builds the
     // csort tables: the planner would pick kCsort whenever they exist
     // (plan_launch); a reproducible one (2) builds them with fixed-point slots
-    const bool ordered = s.tune.deterministic == 1 || s.tune.deterministic == 3;
+    // ... and neither does a mixed handle (fp32 values under fp64 vectors):
+    // csort has no such tables, so it plans as an ordered one
+    const bool ordered = s.tune.deterministic == 1 || s.tune.deterministic == 3 || s.val_dtype != dtype;
     bool want = !ordered && (kf == kCsort || cm == 1);
     // Scattered gathers from an x the L1 cannot hold go to the L2 one line
     // per nonzero, at its request rate, whatever the L2's capacity: until r04
@@ -663,7 +669,7 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
     // at 90.8 us against csort's 62.5 (profiles/r04/auto_regret_f32.jsonl);
     // x of a few L1s (the zoo's `tall`, 16-32 KiB) stays on the row kernels.
     if (!want && kf == kAuto && cm == 0 && !ordered && s.tune.x_slabs == 0 &&
-        !mall_resident(m, n, rp[m], dtype) && (double)n * sv > 256.0 * 1024)
+        !mall_resident(m, n, rp[m], dtype, s.val_dtype) && (double)n * sv > 256.0 * 1024)
       want = irregular_gathers(rp, col, m, sv);
     if (want) {
       if ((rc = build_csort(s, rp, col, val, m, n, dtype, flags))) return rc;
@@ -685,7 +691,7 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
   if (!s.h_tasks.empty()) s.h_xwin_t = xwin_table(rp, col, m, &s.h_tasks, s.tune);
   const int kern = kernel_for_tables(s.A.n_ssr, !s.h_tasks.empty(), flags);
   const bool have_xwin = kern == kCsr3 ? !s.h_xwin_t.empty() : !s.h_xwin.empty();
-  if ((rc = build_xdict(s, rp, col, val, m, n, dtype, flags, have_xwin))) return rc;
+  if ((rc = build_xdict(s, rp, col, val, m, n, flags, have_xwin))) return rc;
   if (s.xd_shape) {  // col_span_bits: the planner's gather-regularity hint
     s.h_xwin.clear();
     s.h_xwin_t.clear();
@@ -705,7 +711,8 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
 // Host planner tables for one shard (needs s.h_rp): split rows (rows longer
 // than kLongRow, cut into kLongChunk pieces), and the device copies of the
 // tables build_row_tables planned (wave tasks, x windows).
-int build_plan_tables(Shard &s, int dtype, unsigned flags) {
+int build_plan_tables(Shard &s, unsigned flags) {
+  const int dtype = s.dtype;  // the vectors' (serial bound, partials); the values': s.val_dtype
   const std::vector<int32_t> &rp = s.h_rp;
   const int64_t m = s.A.m;
   s.dp = DevPlan();
@@ -723,7 +730,7 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags) {
     s.dp.cs = s.csort;
     s.plan.blocks = s.csort.n_wg;
     s.plan.u = s.csort.u;
-    const double alg = hspmv_alg_bytes(s.A.m, s.x_entries, s.A.nnz, dtype, 0, 0);
+    const double alg = alg_bytes_of(s.A.m, s.x_entries, s.A.nnz, dtype, s.val_dtype, 0, 0);
     s.c16_saved = alg - s.csort_format_bytes;
     return HSPMV_OK;
   }
@@ -783,7 +790,7 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags) {
                        s.plan.waves_per_block == 4) ||
                       (s.xd_shape == kCsr3 && s.plan.kernel == kCsr3 && !s.h_tasks.empty() &&
                        s.plan.waves_per_block == s.A.task_waves);
-    const double sv = (double)dtype_size(dtype);
+    const double sv = (double)dtype_size(dtype), sval = (double)dtype_size(s.val_dtype);
     if (fits && s.d_sl_desc) {
       // row slices: the launch reads the slice-major streams, one length per
       // row and one descriptor per task instead of the CSR-order streams and
@@ -804,10 +811,10 @@ int build_plan_tables(Shard &s, int dtype, unsigned flags) {
         (void)hipFree(s.d_val);
         s.d_val = nullptr;
         s.A.val = nullptr;
-        s.bytes -= (int64_t)(sv * (double)s.A.nnz);
+        s.bytes -= (int64_t)(sval * (double)s.A.nnz);
       }
-      s.c16_saved = (double)s.A.nnz * (sv + 4.0) + 4.0 * (double)(m + 1) -
-                    (64.0 * (double)s.sl_padded * sv + (double)s.sl_pos_bytes + (double)m +
+      s.c16_saved = (double)s.A.nnz * (sval + 4.0) + 4.0 * (double)(m + 1) -
+                    (64.0 * (double)s.sl_padded * sval + (double)s.sl_pos_bytes + (double)m +
                      8.0 * (double)(s.sl_desc_n + 1)) -
                     4.0 * (double)(s.xd_runs_n * 2) - 4.0 * (double)s.plan.blocks -
                     sv * (double)(s.xd_entries - s.x_entries);

@@ -239,7 +239,8 @@ bool plan_xdict_for(const int32_t *rp, const int32_t *col, int kern, int64_t m,
 // need no block barrier and were 7 % faster than the dictionaries
 // (53.8 vs 57.9 us, profiles/r01_ab_xdict.jsonl).
 int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n,
-                int dtype, unsigned flags, bool have_xwin) {
+                unsigned flags, bool have_xwin) {
+  const int dtype = s.dtype;  // the dictionaries hold x entries: the cap and the LDS bytes are the vectors'
   s.xd_shape = 0;
   const int mode = s.tune.x_dict > 0 ? 1 : (s.tune.x_dict < 0 ? 0 : -1);  // -1 auto, 0 off, 1 on when it fits
   if (mode == 0 || (flags & HSPMV_FLAG_NO_COL16) || m == 0) return HSPMV_OK;
@@ -251,7 +252,7 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   if (kern == kStream && flag_groups(flags) > 1) return HSPMV_OK;  // groups != 1
   const double sv = (double)dtype_size(dtype);
   const int64_t nnz = rp[m];
-  if (mode < 0 && mall_resident(m, n, nnz, dtype)) return HSPMV_OK;
+  if (mode < 0 && mall_resident(m, n, nnz, dtype, s.val_dtype)) return HSPMV_OK;
   const int32_t long_t = split_threshold(flags);
   XdPlan P;
   // (cuts the task table only when the dictionaries are taken)
@@ -259,8 +260,8 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   // row slices (hspmv_slices.cpp): decided from the rows and the options
   // before the dictionaries are planned, which are then sized for workgroups
   // without product staging
-  const bool slices = slices_why(s.tune, flags, kern, W, rp, m, n, dtype, slice_starts(kern, m, tasks),
-                                 nullptr) == HSPMV_SLICES_OK;
+  const bool slices = slices_why(s.tune, flags, kern, W, rp, m, n, dtype, s.val_dtype,
+                                 slice_starts(kern, m, tasks), nullptr) == HSPMV_SLICES_OK;
   if (!plan_xdict_for(rp, col, kern, m, tasks, W, long_t, xdict_cap_entries(dtype, s.tune), dtype,
                       s.tune, slices, true, P, &s.xd_cut))
     return HSPMV_OK;
@@ -272,7 +273,7 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
     // those are uploaded (the CSR-order values go when the launch is
     // settled, build_plan_tables)
     SlicePlan S;
-    build_slices(rp, P.pos.data(), val, m, dtype, slice_starts(kern, m, s.h_tasks), S);
+    build_slices(rp, P.pos.data(), val, m, s.val_dtype, slice_starts(kern, m, s.h_tasks), S);
     if ((rc = upload_slices(s, S))) return rc;
     s.A.has_slices = true;
   } else if ((rc = upload(s, &s.d_c16, P.pos.data(), 2 * P.pos.size()))) {
@@ -316,6 +317,17 @@ int plan_shape(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_opti
   return HSPMV_OK;
 }
 
+int check_dtype_pair(int val_dtype, int vector_dtype) {
+  if (val_dtype != HSPMV_F32 && val_dtype != HSPMV_F64)
+    return set_error(HSPMV_E_INVALID, "matrix dtype %d (HSPMV_F32 or HSPMV_F64)", val_dtype);
+  if (vector_dtype != HSPMV_F32 && vector_dtype != HSPMV_F64)
+    return set_error(HSPMV_E_INVALID, "vector_dtype %d (HSPMV_F32 or HSPMV_F64)", vector_dtype);
+  if (val_dtype == HSPMV_F64 && vector_dtype == HSPMV_F32)
+    return set_error(HSPMV_E_INVALID, "fp64 values with fp32 vectors are not supported (mixed handles store "
+                                      "fp32 values under fp64 vectors)");
+  return HSPMV_OK;
+}
+
 }  // namespace hspmv
 
 using namespace hspmv;
@@ -344,7 +356,7 @@ int hspmv_xdict_plan_ex(const hspmv_csr *A, const hspmv_csr3_maps *maps, const h
   const bool fill = blk || runs || pos;
   int64_t cut = 0;
   // (sized as a handle with these options would: for the slice kernel when eligible)
-  const bool slices = slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, A->dtype,
+  const bool slices = slices_why(tune, flags, kern, W, A->row_ptr, A->m, A->n, A->dtype, A->dtype,
                                  slice_starts(kern, A->m, tasks), nullptr) == HSPMV_SLICES_OK;
   if (!plan_xdict_for(A->row_ptr, A->col_idx, kern, A->m, tasks, W, long_t,
                       std::min<int64_t>(cap_entries, 65536), A->dtype, tune, slices, fill, P, &cut))

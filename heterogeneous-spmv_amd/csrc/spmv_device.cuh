@@ -280,10 +280,14 @@ struct XWin {
 // C forms the products into LDS; then the row sums.  PF (software
 // pipelining): the next chunk's stage A is issued between this chunk's
 // stage B and C, so its latency overlaps the gather and the sums.
-template <typename T, bool NT, int U, bool PF, int C16, bool XW, bool XD, bool GROUPS, bool PAD = false>
+// TV: the type the values are stored and streamed in (T, or float under
+// T = double: the mixed handles); each value is widened to T once, before its
+// product, so the products and sums are T's.
+template <typename T, bool NT, int U, bool PF, int C16, bool XW, bool XD, bool GROUPS, bool PAD = false,
+          typename TV = T>
 __device__ __forceinline__ void wave_rows(int32_t g0, int32_t g1, int32_t beg, int32_t end,
                                           int32_t long_t, int32_t serial_max, const ColSrc &cs,
-                                          const T *__restrict__ val,
+                                          const TV *__restrict__ val,
                                           const T *__restrict__ x,
                                           T *__restrict__ y, T *lds, int lane,
                                           const XWin<T> &win, bool y_nt, bool carry,
@@ -314,7 +318,7 @@ __device__ __forceinline__ void wave_rows(int32_t g0, int32_t g1, int32_t beg, i
       const unsigned long long coop = coopmask & bits_from(a - g0) & ~bits_from(b - g0);
       const bool mine = serial && row >= a && row < b;
       int32_t col[U];
-      T v[U];
+      TV v[U];
       const gchar *cb = (C16 || XD) ? uniform_ptr(cs.c16 + kb) : uniform_ptr(cs.ci + kb);
       const gchar *vb = uniform_ptr(val + kb);
       // (A raw-buffer form -- SGPR descriptors bounded to the run, no
@@ -357,7 +361,7 @@ __device__ __forceinline__ void wave_rows(int32_t g0, int32_t g1, int32_t beg, i
           } else {
             col[u] = ld_off<NT, int32_t>(cb, j * 4u);
           }
-          v[u] = ld_off<NT, T>(vb, j * (uint32_t)sizeof(T));
+          v[u] = ld_off<NT, TV>(vb, j * (uint32_t)sizeof(TV));
         }
       };
       if constexpr (PF) {
@@ -374,7 +378,7 @@ __device__ __forceinline__ void wave_rows(int32_t g0, int32_t g1, int32_t beg, i
 #pragma unroll
           for (int u = 0; u < U; ++u) {
             xv[u] = XD ? win.xs[col[u]] : win.xs[col[u] - win.lo];
-            vv[u] = v[u];
+            vv[u] = (T)v[u];
           }
         } else {
 #pragma unroll
@@ -383,7 +387,7 @@ __device__ __forceinline__ void wave_rows(int32_t g0, int32_t g1, int32_t beg, i
               xv[u] = T(col[u] & 1) + T(1);
             else
               xv[u] = ld_off<false, T>(xb, (uint32_t)col[u] * (uint32_t)sizeof(T));
-            vv[u] = v[u];
+            vv[u] = (T)v[u];
           }
         }
         if constexpr (PF) {
@@ -559,12 +563,13 @@ __device__ __forceinline__ void stage_xdict(T *xs, const T *__restrict__ x, cons
 // w * groups * 64, loading the next group's row pointers before streaming
 // the current one.  XW: groups whose x window (xwin[g] = {lo, w}) fits
 // kXWin entries gather from an LDS copy of it.
-template <typename T, bool NT, int U, bool PF, int C16, bool XW, bool XD, int W = 4, bool PAD = false>
+template <typename T, bool NT, int U, bool PF, int C16, bool XW, bool XD, int W = 4, bool PAD = false,
+          typename TV = T>
 __global__ __launch_bounds__(W * 64) void hspmv_csr_stream(
     int32_t m, int32_t long_t, int32_t serial_max, uint32_t blk_order, int32_t groups, int32_t y_nt,
     int32_t carry,
     const int32_t *__restrict__ rp, ColSrc cs, const int2 *__restrict__ xwin, XDict xd,
-    const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y) {
+    const TV *__restrict__ val, const T *__restrict__ x, T *__restrict__ y) {
   static_assert(!XD || W == 4, "dictionaries are planned for 256-row blocks");
   __shared__ T lds[W * wave_lds<U, PAD>()];
   __shared__ T xlds[XW ? W * kXWin : 1];
@@ -609,7 +614,7 @@ __global__ __launch_bounds__(W * 64) void hspmv_csr_stream(
     if (g1 < gend) group_bounds(rp, g1, (int32_t)min<int64_t>(g1 + kWave, gend), lane, nbeg, nend);
     int32_t gbase = 0;
     if constexpr (C16 == 2) gbase = (int32_t)sload_i64(cs.cbase, (uint64_t)(g0 / kWave) * 4u);
-    wave_rows<T, NT, U, PF, C16, XW, XD, false, PAD>((int32_t)g0, g1, beg, end, long_t, serial_max, cs, val,
+    wave_rows<T, NT, U, PF, C16, XW, XD, false, PAD, TV>((int32_t)g0, g1, beg, end, long_t, serial_max, cs, val,
                                                      x, y, my,
                                          lane, win, y_nt != 0, carry != 0, gbase, ts);
     ts = nullptr;  // trace the first group only
@@ -620,12 +625,12 @@ __global__ __launch_bounds__(W * 64) void hspmv_csr_stream(
   }
 }
 
-template <typename T, bool NT, int U, bool PF, int C16, int W, bool XW, bool XD>
+template <typename T, bool NT, int U, bool PF, int C16, int W, bool XW, bool XD, typename TV = T>
 __global__ __launch_bounds__(W * 64) void hspmv_csr3(
     int32_t n_tasks, int32_t long_t, int32_t serial_max, uint32_t blk_order, int32_t y_nt, int32_t carry,
     int32_t align,
     const int32_t *__restrict__ task_start, const int2 *__restrict__ xwin, XDict xd,
-    const int32_t *__restrict__ rp, ColSrc cs, const T *__restrict__ val,
+    const int32_t *__restrict__ rp, ColSrc cs, const TV *__restrict__ val,
     const T *__restrict__ x, T *__restrict__ y) {
   __shared__ T lds[W * wave_lds<U, false>()];
   __shared__ T xlds[XW ? W * kXWin : 1];
@@ -685,7 +690,7 @@ __global__ __launch_bounds__(W * 64) void hspmv_csr3(
   for (int32_t g0 = r0, g1 = g1_first; g0 < r1; g0 = g1, g1 = min(g1 + kWave, r1)) {
     int32_t nbeg = 0, nend = 0;
     if (g1 < r1) group_bounds(rp, g1, min(g1 + kWave, r1), lane, nbeg, nend);
-    wave_rows<T, NT, U, PF, C16, XW, XD, HSPMV_COOP_GROUPS != 0>(g0, g1, beg, end, long_t, serial_max, cs, val,
+    wave_rows<T, NT, U, PF, C16, XW, XD, HSPMV_COOP_GROUPS != 0, false, TV>(g0, g1, beg, end, long_t, serial_max, cs, val,
                                                                  x, y, my, lane,
                                          win, y_nt != 0, carry != 0, gbase, ts);
     ts = nullptr;
@@ -739,22 +744,22 @@ __device__ __forceinline__ sl_i4 sload_i128(const void *p, uint64_t byte_off) {
 
 typedef uint32_t sl_u3 __attribute__((ext_vector_type(3), aligned(4)));
 
-template <typename T, int B>
+template <typename TV, int B>
 struct SliceBatch {
-  T v[B];               // slot k0 + i of the lane's row
+  TV v[B];              // slot k0 + i of the lane's row, as stored
   uint32_t pq[B / 2];   // positions of whole 4-slot groups, two per register (PB = 12: 3 per 8 slots)
   uint32_t ps[3];       // positions of the slice's last 1-3 slots (single columns)
 };
 
 // A whole batch: slots [k0, k0 + B) all lie in 16-byte value groups and
 // 8-byte (PB = 12: 12-byte) position groups.  vb / pb: the slice's streams.
-template <typename T, bool NT, int B, int PB>
-__device__ __forceinline__ void slice_load_full(SliceBatch<T, B> &q, const gchar *vb, const gchar *pb,
+template <typename TV, bool NT, int B, int PB>
+__device__ __forceinline__ void slice_load_full(SliceBatch<TV, B> &q, const gchar *vb, const gchar *pb,
                                                 int32_t k0, int lane) {
-  constexpr int G = 16 / (int)sizeof(T);
-  typedef T tv __attribute__((ext_vector_type(G)));
+  constexpr int G = 16 / (int)sizeof(TV);
+  typedef TV tv __attribute__((ext_vector_type(G)));
   typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-  const gchar *vbb = vb + (uint64_t)(uint32_t)k0 * (kWave * sizeof(T));
+  const gchar *vbb = vb + (uint64_t)(uint32_t)k0 * (kWave * sizeof(TV));
   const gchar *pbb = pb + (uint64_t)(uint32_t)k0 * (kWave * PB / 8u);
 #pragma unroll
   for (int j = 0; j < B / G; ++j) {
@@ -785,16 +790,16 @@ __device__ __forceinline__ void slice_load_full(SliceBatch<T, B> &q, const gchar
 // as above, the rest from the single columns.  Slots past w read as value 0
 // at position 0 (and are masked like every slot past a row's end).  The
 // tail's positions are 16-bit for either PB; PB sets where they start.
-template <typename T, bool NT, int B, int PB>
-__device__ __forceinline__ void slice_load_tail(SliceBatch<T, B> &q, const gchar *vb, const gchar *pb,
+template <typename TV, bool NT, int B, int PB>
+__device__ __forceinline__ void slice_load_tail(SliceBatch<TV, B> &q, const gchar *vb, const gchar *pb,
                                                 int32_t k0, int32_t w, int lane) {
-  constexpr int G = 16 / (int)sizeof(T);
-  typedef T tv __attribute__((ext_vector_type(G)));
+  constexpr int G = 16 / (int)sizeof(TV);
+  typedef TV tv __attribute__((ext_vector_type(G)));
   typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-  const gchar *vbb = vb + (uint64_t)(uint32_t)k0 * (kWave * sizeof(T));
+  const gchar *vbb = vb + (uint64_t)(uint32_t)k0 * (kWave * sizeof(TV));
   const gchar *pbb = pb + (uint64_t)(uint32_t)k0 * (kWave * PB / 8u);
 #pragma unroll
-  for (int i = 0; i < B; ++i) q.v[i] = T(0);
+  for (int i = 0; i < B; ++i) q.v[i] = TV(0);
 #pragma unroll
   for (int i = 0; i < B / 2; ++i) q.pq[i] = 0u;
 #pragma unroll
@@ -809,7 +814,7 @@ __device__ __forceinline__ void slice_load_tail(SliceBatch<T, B> &q, const gchar
 #pragma unroll
       for (int e = 0; e < G - 1; ++e)
         if (k0 + j * G + e < w)
-          q.v[j * G + e] = ld_off<NT, T>(vbb, (uint32_t)((j * G + e) * kWave + lane) * (uint32_t)sizeof(T));
+          q.v[j * G + e] = ld_off<NT, TV>(vbb, (uint32_t)((j * G + e) * kWave + lane) * (uint32_t)sizeof(TV));
     }
   }
 #pragma unroll
@@ -843,9 +848,10 @@ __device__ __forceinline__ uint32_t slice_pos(const uint32_t *pq, int i) {
 // Adds the batch's slots to acc in slot order: the product rounded on its
 // own (-ffp-contract=off), then the add; a slot at or past the row's end
 // leaves acc as it is.  full: every position comes from pq, PB bits each
-// (a tail batch's are 16-bit).
-template <typename T, int B, int PB>
-__device__ __forceinline__ T slice_consume(T acc, const SliceBatch<T, B> &q, const T *xs, int32_t k0,
+// (a tail batch's are 16-bit).  A value stored narrower than T (TV) is
+// widened here, once, before its product.
+template <typename T, int B, int PB, typename TV>
+__device__ __forceinline__ T slice_consume(T acc, const SliceBatch<TV, B> &q, const T *xs, int32_t k0,
                                            int32_t w, int32_t len, bool full) {
   T xv[B];
 #pragma unroll
@@ -856,7 +862,7 @@ __device__ __forceinline__ T slice_consume(T acc, const SliceBatch<T, B> &q, con
   }
 #pragma unroll
   for (int i = 0; i < B; ++i) {
-    const T p = q.v[i] * xv[i];
+    const T p = (T)q.v[i] * xv[i];
     acc = (k0 + i < len) ? acc + p : acc;
   }
   return acc;
@@ -868,12 +874,13 @@ __device__ __forceinline__ T slice_consume(T acc, const SliceBatch<T, B> &q, con
 // rows' lengths before the staging; after the barrier it walks the slot
 // columns in batches of B, the next batch's loads issued before the current
 // one is consumed.  LDS: the dictionary alone.
-template <typename T, bool NT, int B, int PB>
+template <typename T, bool NT, int B, int PB, typename TV = T>
 __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t blk_order, int32_t y_nt,
-                                                    Slices sl, XDict xd, const T *__restrict__ val,
+                                                    Slices sl, XDict xd, const TV *__restrict__ val,
                                                     const T *__restrict__ x, T *__restrict__ y) {
   static_assert(B % 4 == 0 && B >= 4, "batches hold whole position groups");
   static_assert(PB == 16 || (PB == 12 && B % 8 == 0), "12-bit positions come in groups of 8 slots");
+  static_assert(B % (16 / (int)sizeof(TV)) == 0, "batches hold whole 16-byte value groups");
   extern __shared__ __attribute__((aligned(16))) unsigned char xdyn[];
   const int wid = threadIdx.x >> 6;
   const int lane = threadIdx.x & (kWave - 1);
@@ -897,21 +904,21 @@ __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t b
   const gchar *pb = uniform_ptr(sl.pos + (int64_t)poff * kWave);
   const int32_t wf = w & ~(B - 1);  // slots in whole batches
   T acc = T(0);
-  SliceBatch<T, B> cur, nxt, tail;
+  SliceBatch<TV, B> cur, nxt, tail;
   int32_t k0 = 0;
-  if (wf > 0) slice_load_full<T, NT, B, PB>(cur, vb, pb, 0, lane);
+  if (wf > 0) slice_load_full<TV, NT, B, PB>(cur, vb, pb, 0, lane);
   for (; k0 + 3 * B <= wf; k0 += 2 * B) {
-    slice_load_full<T, NT, B, PB>(nxt, vb, pb, k0 + B, lane);
+    slice_load_full<TV, NT, B, PB>(nxt, vb, pb, k0 + B, lane);
     __builtin_amdgcn_sched_barrier(0);
     acc = slice_consume<T, B, PB>(acc, cur, xs, k0, w, len, true);
     __builtin_amdgcn_sched_barrier(0);
-    slice_load_full<T, NT, B, PB>(cur, vb, pb, k0 + 2 * B, lane);
+    slice_load_full<TV, NT, B, PB>(cur, vb, pb, k0 + 2 * B, lane);
     __builtin_amdgcn_sched_barrier(0);
     acc = slice_consume<T, B, PB>(acc, nxt, xs, k0 + B, w, len, true);
     __builtin_amdgcn_sched_barrier(0);
   }
   if (k0 + 2 * B <= wf) {
-    slice_load_full<T, NT, B, PB>(nxt, vb, pb, k0 + B, lane);
+    slice_load_full<TV, NT, B, PB>(nxt, vb, pb, k0 + B, lane);
     __builtin_amdgcn_sched_barrier(0);
     acc = slice_consume<T, B, PB>(acc, cur, xs, k0, w, len, true);
     __builtin_amdgcn_sched_barrier(0);
@@ -919,7 +926,7 @@ __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t b
     k0 += B;
   }
   // cur: the last whole batch (at wf - B), not yet added
-  if (w > wf) slice_load_tail<T, NT, B, PB>(tail, vb, pb, wf, w, lane);
+  if (w > wf) slice_load_tail<TV, NT, B, PB>(tail, vb, pb, wf, w, lane);
   __builtin_amdgcn_sched_barrier(0);
   if (wf > 0) acc = slice_consume<T, B, PB>(acc, cur, xs, wf - B, w, len, true);
   if (w > wf) acc = slice_consume<T, B, 16>(acc, tail, xs, wf, w, len, false);
@@ -941,30 +948,30 @@ inline uint32_t block_order(const LaunchPlan &p) {
   return (uint32_t)p.xcd_chunk | (p.reverse ? kSweepReverse : 0u);
 }
 
-template <typename T, int PB>
+template <typename T, int PB, typename TV>
 void launch_slices_pb(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st) {
   const Slices sl{dp.sl_desc, dp.sl_len, dp.sl_pos, dp.sl_ppre};
   const XDict xd{dp.xd_blk, reinterpret_cast<const int2 *>(dp.xd_runs)};
   const unsigned dyn = (unsigned)dp.xd_lds_bytes + (unsigned)p.dyn_lds;
-  const T *val = static_cast<const T *>(dp.sl_val);
+  const TV *val = static_cast<const TV *>(dp.sl_val);
   if (p.nontemporal)
-    hipLaunchKernelGGL((hspmv_slices<T, true, HSPMV_SLICE_BATCH, PB>), dim3((unsigned)p.blocks), dim3(256), dyn,
+    hipLaunchKernelGGL((hspmv_slices<T, true, HSPMV_SLICE_BATCH, PB, TV>), dim3((unsigned)p.blocks), dim3(256), dyn,
                        st, dp.n_slices, block_order(p), (int32_t)p.y_nt, sl, xd, val, x, y);
   else
-    hipLaunchKernelGGL((hspmv_slices<T, false, HSPMV_SLICE_BATCH, PB>), dim3((unsigned)p.blocks), dim3(256), dyn,
+    hipLaunchKernelGGL((hspmv_slices<T, false, HSPMV_SLICE_BATCH, PB, TV>), dim3((unsigned)p.blocks), dim3(256), dyn,
                        st, dp.n_slices, block_order(p), (int32_t)p.y_nt, sl, xd, val, x, y);
 }
 
-template <typename T>
+template <typename T, typename TV>
 hipError_t launch_slices(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st) {
   if (!dp.xd_blk || !dp.sl_len || !dp.sl_pos || !dp.sl_val || p.waves_per_block != 4 ||
       p.blocks != ((int64_t)dp.n_slices + 3) / 4 ||
       !(dp.sl_pos_bits == 16 || (dp.sl_pos_bits == 12 && dp.sl_ppre)))
     return hipErrorInvalidValue;  // the host built the slices for another block shape
   if (dp.sl_pos_bits == 12)
-    launch_slices_pb<T, 12>(dp, p, x, y, st);
+    launch_slices_pb<T, 12, TV>(dp, p, x, y, st);
   else
-    launch_slices_pb<T, 16>(dp, p, x, y, st);
+    launch_slices_pb<T, 16, TV>(dp, p, x, y, st);
   return hipGetLastError();
 }
 
@@ -972,10 +979,10 @@ inline ColSrc col_src(const DevCSR &A) {
   return ColSrc{A.col_idx, A.col16, A.cbase, A.cplanes, A.n_cplanes, A.cplane_words};
 }
 
-template <typename T, bool NT, int U, bool PF, int C16, bool XD>
+template <typename T, bool NT, int U, bool PF, int C16, bool XD, typename TV>
 void launch_rows_u(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const T *x, T *y,
                    hipStream_t st) {
-  const T *val = static_cast<const T *>(A.val);
+  const TV *val = static_cast<const TV *>(A.val);
   const ColSrc cs = col_src(A);
   const XDict xd{dp.xd_blk, reinterpret_cast<const int2 *>(dp.xd_runs)};
   // dynamic LDS: the block's x dictionary (XD), or occupancy experiments (HSPMV_DYNLDS)
@@ -983,7 +990,7 @@ void launch_rows_u(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, cons
   if (p.kernel == kStream) {
     const int2 *xw = reinterpret_cast<const int2 *>(dp.xwin);
 #define HSPMV_STREAM(C, XW, XDX, W, PAD)                                                            \
-  hipLaunchKernelGGL((hspmv_csr_stream<T, NT, U, PF, C, XW, XDX, W, PAD>), dim3((unsigned)p.blocks), \
+  hipLaunchKernelGGL((hspmv_csr_stream<T, NT, U, PF, C, XW, XDX, W, PAD, TV>), dim3((unsigned)p.blocks), \
                      dim3(W * 64), dyn, st, A.m, dp.long_t, dp.serial_max, block_order(p),       \
                      (int32_t)p.groups,                                                               \
                      (int32_t)p.y_nt, p.carry, A.row_ptr, cs, xw, xd, val, x, y)
@@ -1016,7 +1023,7 @@ void launch_rows_u(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, cons
   {
   const int2 *xw = reinterpret_cast<const int2 *>(dp.xwin);
 #define HSPMV_CSR3(W, C, XW, X)                                                               \
-  hipLaunchKernelGGL((hspmv_csr3<T, NT, U, PF, C, W, XW, X>), dim3((unsigned)p.blocks),      \
+  hipLaunchKernelGGL((hspmv_csr3<T, NT, U, PF, C, W, XW, X, TV>), dim3((unsigned)p.blocks),      \
                      dim3(W * 64), dyn, st, dp.n_tasks, dp.long_t, dp.serial_max,             \
                      block_order(p),                                                   \
                      (int32_t)p.y_nt, p.carry, dp.task_align, dp.task_start, xw, xd, A.row_ptr, cs, \
@@ -1043,51 +1050,52 @@ void launch_rows_u(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, cons
   }
 }
 
-template <typename T, bool NT, bool PF, int C16, bool XD>
+template <typename T, bool NT, bool PF, int C16, bool XD, typename TV>
 hipError_t launch_rows_pf(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const T *x,
                           T *y, hipStream_t st) {
   switch (p.u) {
-    case 2: launch_rows_u<T, NT, 2, PF, C16, XD>(A, dp, p, x, y, st); break;
-    case 3: launch_rows_u<T, NT, 3, PF, C16, XD>(A, dp, p, x, y, st); break;
-    case 4: launch_rows_u<T, NT, 4, PF, C16, XD>(A, dp, p, x, y, st); break;
-    case 5: launch_rows_u<T, NT, 5, PF, C16, XD>(A, dp, p, x, y, st); break;
-    case 6: launch_rows_u<T, NT, 6, PF, C16, XD>(A, dp, p, x, y, st); break;
-    case 8: launch_rows_u<T, NT, 8, PF, C16, XD>(A, dp, p, x, y, st); break;
-    case 16: launch_rows_u<T, NT, 16, PF, C16, XD>(A, dp, p, x, y, st); break;
+    case 2: launch_rows_u<T, NT, 2, PF, C16, XD, TV>(A, dp, p, x, y, st); break;
+    case 3: launch_rows_u<T, NT, 3, PF, C16, XD, TV>(A, dp, p, x, y, st); break;
+    case 4: launch_rows_u<T, NT, 4, PF, C16, XD, TV>(A, dp, p, x, y, st); break;
+    case 5: launch_rows_u<T, NT, 5, PF, C16, XD, TV>(A, dp, p, x, y, st); break;
+    case 6: launch_rows_u<T, NT, 6, PF, C16, XD, TV>(A, dp, p, x, y, st); break;
+    case 8: launch_rows_u<T, NT, 8, PF, C16, XD, TV>(A, dp, p, x, y, st); break;
+    case 16: launch_rows_u<T, NT, 16, PF, C16, XD, TV>(A, dp, p, x, y, st); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
-template <typename T, int C16, bool XD>
+template <typename T, int C16, bool XD, typename TV>
 hipError_t launch_rows_c(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const T *x,
                          T *y, hipStream_t st) {
   if (p.nontemporal)
-    return p.prefetch ? launch_rows_pf<T, true, true, C16, XD>(A, dp, p, x, y, st)
-                      : launch_rows_pf<T, true, false, C16, XD>(A, dp, p, x, y, st);
-  return p.prefetch ? launch_rows_pf<T, false, true, C16, XD>(A, dp, p, x, y, st)
-                    : launch_rows_pf<T, false, false, C16, XD>(A, dp, p, x, y, st);
+    return p.prefetch ? launch_rows_pf<T, true, true, C16, XD, TV>(A, dp, p, x, y, st)
+                      : launch_rows_pf<T, true, false, C16, XD, TV>(A, dp, p, x, y, st);
+  return p.prefetch ? launch_rows_pf<T, false, true, C16, XD, TV>(A, dp, p, x, y, st)
+                    : launch_rows_pf<T, false, false, C16, XD, TV>(A, dp, p, x, y, st);
 }
 
 // XD (block x dictionaries) replaces both the 32-bit columns and the col16
-// offsets: its col stream is the 16-bit xs positions.
-template <typename T>
+// offsets: its col stream is the 16-bit xs positions.  TV: the stored type of
+// A.val / dp.sl_val (the mixed handles: float under T = double).
+template <typename T, typename TV = T>
 hipError_t launch_rows(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const T *x, T *y,
                        hipStream_t st) {
-  if (dp.sl_desc) return launch_slices<T>(dp, p, x, y, st);  // row slices of a dictionary handle
+  if (dp.sl_desc) return launch_slices<T, TV>(dp, p, x, y, st);  // row slices of a dictionary handle
   if (dp.xd_blk) {
     if (!A.col16 || (p.kernel == kStream && p.groups != 1) ||
         (p.kernel == kCsr3 && (!dp.task_start || (p.waves_per_block != 4 && p.waves_per_block != 8))))
       return hipErrorInvalidValue;  // the host built the dictionary for another block shape
-    return launch_rows_c<T, 0, true>(A, dp, p, x, y, st);
+    return launch_rows_c<T, 0, true, TV>(A, dp, p, x, y, st);
   }
   if (A.col16 && A.c16_mode == 2) {
     if (p.kernel == kCsr3 && !dp.task_start)
       return hipErrorInvalidValue;  // built for the host-planned wave tasks (one base per task)
-    return launch_rows_c<T, 2, false>(A, dp, p, x, y, st);
+    return launch_rows_c<T, 2, false, TV>(A, dp, p, x, y, st);
   }
-  return A.col16 ? launch_rows_c<T, 1, false>(A, dp, p, x, y, st)
-                 : launch_rows_c<T, 0, false>(A, dp, p, x, y, st);
+  return A.col16 ? launch_rows_c<T, 1, false, TV>(A, dp, p, x, y, st)
+                 : launch_rows_c<T, 0, false, TV>(A, dp, p, x, y, st);
 }
 
 }  // namespace dev

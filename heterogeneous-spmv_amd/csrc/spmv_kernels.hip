@@ -90,10 +90,13 @@ __device__ __forceinline__ T wave_sum(T v) {
   return v;
 }
 
-template <typename T, int L, bool NT>
+// TV (here and in the split-row kernels): the stored type of val -- T, or
+// float under T = double for the mixed handles; a value is widened to T before
+// its product.
+template <typename T, int L, bool NT, typename TV = T>
 __global__ __launch_bounds__(256) void hspmv_csr_vector(
     int32_t m, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
-    const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y) {
+    const TV *__restrict__ val, const T *__restrict__ x, T *__restrict__ y) {
   const int lane = threadIdx.x & (L - 1);
   int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / L;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x / L;
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(256) void hspmv_csr_vector(
     const int32_t end = rp[row + 1];
     T s = T(0);
     for (int32_t k = beg + lane; k < end; k += L)
-      s = fma(ldg<NT>(val + k), x[ldg<NT>(ci + k)], s);
+      s = fma((T)ldg<NT>(val + k), x[ldg<NT>(ci + k)], s);
 #pragma unroll
     for (int off = L / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, L);
     if (lane == 0) y[row] = s;
@@ -111,10 +114,10 @@ __global__ __launch_bounds__(256) void hspmv_csr_vector(
 
 // Split rows, step 1: one 256-thread workgroup per chunk of <= kLongChunk
 // nonzeros of one long row -> partials[chunk].
-template <typename T, bool NT>
+template <typename T, bool NT, typename TV = T>
 __global__ __launch_bounds__(256) void hspmv_long_chunks(
     int32_t n_chunks, const int32_t *__restrict__ chunk_k, const int32_t *__restrict__ ci,
-    const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ partials) {
+    const TV *__restrict__ val, const T *__restrict__ x, T *__restrict__ partials) {
   __shared__ T red[4];
   const int c = blockIdx.x;
   if (c >= n_chunks) return;  // block-uniform
@@ -122,10 +125,10 @@ __global__ __launch_bounds__(256) void hspmv_long_chunks(
   T s0 = T(0), s1 = T(0);
   int32_t k = k0 + threadIdx.x;
   for (; k + 256 < k1; k += 512) {
-    s0 = fma(ldg<NT>(val + k), x[ldg<NT>(ci + k)], s0);
-    s1 = fma(ldg<NT>(val + k + 256), x[ldg<NT>(ci + k + 256)], s1);
+    s0 = fma((T)ldg<NT>(val + k), x[ldg<NT>(ci + k)], s0);
+    s1 = fma((T)ldg<NT>(val + k + 256), x[ldg<NT>(ci + k + 256)], s1);
   }
-  if (k < k1) s0 = fma(ldg<NT>(val + k), x[ldg<NT>(ci + k)], s0);
+  if (k < k1) s0 = fma((T)ldg<NT>(val + k), x[ldg<NT>(ci + k)], s0);
   const T s = wave_sum(s0 + s1);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -159,10 +162,10 @@ __global__ __launch_bounds__(256) void hspmv_long_reduce(
 // adds (C5's 144 616-nonzero hub row: 2.1 ms for the launch).
 constexpr int kLongSerialBytes = 16384;  // per LDS buffer (two: 32 KiB)
 
-template <typename T, bool NT>
+template <typename T, bool NT, typename TV = T>
 __global__ __launch_bounds__(256) void hspmv_long_serial(
     int32_t n_long, const int32_t *__restrict__ long_row, const int32_t *__restrict__ rp,
-    const int32_t *__restrict__ ci, const T *__restrict__ val, const T *__restrict__ x,
+    const int32_t *__restrict__ ci, const TV *__restrict__ val, const T *__restrict__ x,
     T *__restrict__ y, T *__restrict__ lsum) {
   constexpr int32_t kLongSerialChunk = kLongSerialBytes / (int)sizeof(T);
   __shared__ __attribute__((aligned(16))) T buf[2][kLongSerialChunk];
@@ -173,7 +176,7 @@ __global__ __launch_bounds__(256) void hspmv_long_serial(
   auto fill = [&](T *dst, int32_t c, int t, int nt) {
     const int32_t n = min(k1 - c, kLongSerialChunk);
     for (int32_t i = t; i < n; i += nt) {
-      const T p = ldg<NT>(val + c + i) * x[ldg<NT>(ci + c + i)];
+      const T p = (T)ldg<NT>(val + c + i) * x[ldg<NT>(ci + c + i)];
       dst[i] = p;
     }
   };
@@ -239,13 +242,28 @@ __global__ __launch_bounds__(256) void hspmv_long_scatter(int32_t n_long, const 
 
 // ------------------------------------------------------------------ dispatch
 
-template <typename T, bool NT>
+// The row kernels' instantiation unit for vectors of T and values stored as TV.
+template <typename TV>
+hipError_t launch_rows_of(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const double *x, double *y,
+                          hipStream_t st) {
+  if constexpr (sizeof(TV) == 8)
+    return launch_rows_f64(A, dp, p, x, y, st);
+  else
+    return launch_rows_f32v64(A, dp, p, x, y, st);
+}
+template <typename TV>
+hipError_t launch_rows_of(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const float *x, float *y,
+                          hipStream_t st) {
+  return launch_rows_f32(A, dp, p, x, y, st);
+}
+
+template <typename T, bool NT, typename TV = T>
 hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const T *x,
                         T *y, hipStream_t st) {
   if (A.m == 0) return hipSuccess;
   const int32_t *rp = A.row_ptr;
   const int32_t *ci = A.col_idx;
-  const T *val = static_cast<const T *>(A.val);
+  const TV *val = static_cast<const TV *>(A.val);
   hipError_t e = hipSuccess;
   // serial order: the long rows' workgroups start first, on their own
   // stream (forked from st, joined back below), beside the row kernel, and
@@ -256,7 +274,7 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
     if ((e = hipEventRecord(dp.long_fork, st)) != hipSuccess ||
         (e = hipStreamWaitEvent(dp.long_stream, dp.long_fork, 0)) != hipSuccess)
       return e;
-    hipLaunchKernelGGL((hspmv_long_serial<T, NT>), dim3((unsigned)dp.n_long), dim3(256), 0, dp.long_stream,
+    hipLaunchKernelGGL((hspmv_long_serial<T, NT, TV>), dim3((unsigned)dp.n_long), dim3(256), 0, dp.long_stream,
                        dp.n_long, dp.long_row, rp, ci, val, x, y, static_cast<T *>(dp.partials));
     if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(dp.long_join, dp.long_stream)) != hipSuccess)
       return e;
@@ -266,7 +284,7 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
       switch (p.lanes) {
 #define HSPMV_VEC(L)                                                                    \
   case L:                                                                               \
-    hipLaunchKernelGGL((hspmv_csr_vector<T, L, NT>), dim3((unsigned)p.blocks), dim3(256), \
+    hipLaunchKernelGGL((hspmv_csr_vector<T, L, NT, TV>), dim3((unsigned)p.blocks), dim3(256), \
                        0, st, A.m, rp, ci, val, x, y);                                  \
     break;
         HSPMV_VEC(1) HSPMV_VEC(2) HSPMV_VEC(4) HSPMV_VEC(8) HSPMV_VEC(16)
@@ -290,19 +308,15 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
         for (int32_t b = 0; b < dp.n_slabs && e == hipSuccess; ++b) {
           As.row_ptr = dp.slab_rp + (size_t)b * (size_t)(A.m + 1);
           ps.carry = b > 0;
-          if constexpr (sizeof(T) == 8)
-            e = launch_rows_f64(As, dp, ps, x, y, st);
-          else
-            e = launch_rows_f32(As, dp, ps, x, y, st);
+          e = launch_rows_of<TV>(As, dp, ps, x, y, st);  // (mixed: slab_val is fp32 as well)
         }
-      } else if constexpr (sizeof(T) == 8) {
-        e = launch_rows_f64(A, dp, p, x, y, st);
       } else {
-        e = launch_rows_f32(A, dp, p, x, y, st);
+        e = launch_rows_of<TV>(A, dp, p, x, y, st);
       }
       if (e != hipSuccess) return e;
       break;
     case kCsort:
+      if constexpr (sizeof(TV) != sizeof(T)) return hipErrorInvalidValue;  // no mixed csort tables
       return launch_csort(dp.cs, sizeof(T) == 8 ? 1 : 0, x, y, st);
     default:
       return hipErrorInvalidValue;
@@ -314,11 +328,11 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
                        dp.n_long, dp.long_row, static_cast<const T *>(dp.partials), y);
     e = hipGetLastError();
   } else if (dp.n_long > 0 && dp.long_serial) {
-    hipLaunchKernelGGL((hspmv_long_serial<T, NT>), dim3((unsigned)dp.n_long), dim3(256), 0, st, dp.n_long,
+    hipLaunchKernelGGL((hspmv_long_serial<T, NT, TV>), dim3((unsigned)dp.n_long), dim3(256), 0, st, dp.n_long,
                        dp.long_row, rp, ci, val, x, y, static_cast<T *>(nullptr));
     e = hipGetLastError();
   } else if (dp.n_long > 0) {
-    hipLaunchKernelGGL((hspmv_long_chunks<T, NT>), dim3((unsigned)dp.n_chunks), dim3(256), 0, st,
+    hipLaunchKernelGGL((hspmv_long_chunks<T, NT, TV>), dim3((unsigned)dp.n_chunks), dim3(256), 0, st,
                        dp.n_chunks, dp.chunk_k, ci, val, x, static_cast<T *>(dp.partials));
     hipLaunchKernelGGL((hspmv_long_reduce<T>), dim3((unsigned)((dp.n_long + 3) / 4)), dim3(256),
                        0, st, dp.n_long, dp.long_row, dp.long_cstart,
@@ -330,10 +344,16 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
 
 }  // namespace
 
-hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, const LaunchPlan &fwd,
+hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, int val_dtype, const LaunchPlan &fwd,
                        const void *x, void *y, hipStream_t stream, bool reverse) {
   LaunchPlan plan = fwd;
   plan.reverse = reverse && (fwd.kernel == kStream || fwd.kernel == kCsr3);
+  if (dtype == HSPMV_F64 && val_dtype == HSPMV_F32) {  // mixed: fp32 values under fp64 vectors and sums
+    return plan.nontemporal
+               ? launch_typed<double, true, float>(A, dp, plan, (const double *)x, (double *)y, stream)
+               : launch_typed<double, false, float>(A, dp, plan, (const double *)x, (double *)y, stream);
+  }
+  if (dtype != val_dtype) return hipErrorInvalidValue;
   if (dtype == 1) {
     return plan.nontemporal
                ? launch_typed<double, true>(A, dp, plan, (const double *)x, (double *)y, stream)

@@ -200,6 +200,10 @@ SIGNATURES = {
                                        C.POINTER(C.c_int), C.c_int, C.c_uint]),
     "hspmv_create_ex": (C.c_int, [C.POINTER(_H), C.POINTER(Csr), C.POINTER(Csr3Maps),
                                   C.POINTER(Options)]),
+    "hspmv_create_mixed": (C.c_int, [C.POINTER(_H), C.POINTER(Csr), C.POINTER(Csr3Maps),
+                                     C.POINTER(Options), C.c_int]),
+    "hspmv_get_dtypes": (C.c_int, [_H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hspmv_values_fit_f32": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     "hspmv_set_x": (C.c_int, [_H, _P]),
     "hspmv_bind_x_device": (C.c_int, [_H, _P]),
     "hspmv_bind_y_device": (C.c_int, [_H, _P]),
@@ -250,6 +254,9 @@ SIGNATURES = {
     "hspmv_slices_plan": (C.c_int, [C.POINTER(Csr), C.POINTER(Csr3Maps), C.POINTER(Options),
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int32), _P, _P, _P, _P]),
+    "hspmv_slices_plan_vec": (C.c_int, [C.POINTER(Csr), C.POINTER(Csr3Maps), C.POINTER(Options), C.c_int,
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "hspmv_slices_pack": (C.c_int, [C.c_int64, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P, _P]),
     "hspmv_alg_bytes": (C.c_double, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64]),
     "hspmv_device_count": (C.c_int, [C.POINTER(C.c_int)]),

@@ -81,6 +81,12 @@ class CsrMatrix:
         return _lib.Csr(self.m, self.n, self.nnz, _ptr(self.row_ptr), _ptr(self.col_idx),
                         _ptr(self.val), dtype_code(self.val.dtype))
 
+    def fits_float32(self) -> bool:
+        """True when every value converts to float32 and back to the same bits
+        (hspmv_values_fit_f32), so ``SpMV(A.astype(np.float32),
+        vector_dtype=np.float64)`` gives the float64 operator's y bit for bit."""
+        return values_fit_float32(self.val)[0]
+
     @classmethod
     def from_scipy(cls, S, dtype=np.float64) -> "CsrMatrix":
         S = S.tocsr()
@@ -296,12 +302,28 @@ def xdict_plan(A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, kernel: str = "
     return blk, runs, pos[:A.nnz]
 
 
+def values_fit_float32(val: np.ndarray):
+    """(fits, first_bad) of hspmv_values_fit_f32 for a float32 / float64 array:
+    first_bad is the first index whose float32 round trip changes its bits, or
+    None when every value fits."""
+    val = np.ascontiguousarray(val)
+    bad = C.c_int64(-1)
+    rc = lib().hspmv_values_fit_f32(_ptr(val), int(val.shape[0]), dtype_code(val.dtype), C.byref(bad))
+    if rc < 0:
+        check(rc, "hspmv_values_fit_f32")
+    return (True, None) if rc == 1 else (False, int(bad.value))
+
+
 def slices_plan(A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, kernel: str = "auto",
-                split: bool = True, options: Optional[dict] = None, fill: bool = True) -> dict:
+                split: bool = True, options: Optional[dict] = None, fill: bool = True,
+                vector_dtype=None) -> dict:
     """Row slices the library would build for A (hspmv_slices_plan): a dict
     with ``why`` (a _lib.SLICES_WHY name; "ok" = eligible), ``n_desc``,
     ``n_slices``, ``padded_entries`` and -- when eligible and ``fill`` --
-    ``desc`` ((n_desc + 1, 2) {prefix, first row}), ``len``, ``pos``, ``val``."""
+    ``desc`` ((n_desc + 1, 2) {prefix, first row}), ``len``, ``pos``, ``val``.
+    ``vector_dtype`` (None: A's dtype): the plan of a handle whose x and y are
+    of that type (hspmv_slices_plan_vec; float64 over a float32 A: the mixed
+    handle's, ``val`` stays float32)."""
     cs = A.c_struct()
     ms = maps.c_struct() if maps is not None else None
     flags = _KERNELS[kernel] | (0 if split else _lib.FLAG_NO_SPLIT)
@@ -310,7 +332,15 @@ def slices_plan(A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, kernel: str = 
     L = lib()
     args = (C.byref(cs), C.byref(ms) if ms is not None else None, C.byref(opt),
             C.byref(nd), C.byref(ns), C.byref(pe), C.byref(why))
-    check(L.hspmv_slices_plan(*args, None, None, None, None), "slices_plan")
+    if vector_dtype is not None:
+        vdt = dtype_code(vector_dtype)
+        args = args[:3] + (vdt,) + args[3:]
+
+        def plan_fn(*a):
+            return L.hspmv_slices_plan_vec(*a)
+    else:
+        plan_fn = L.hspmv_slices_plan
+    check(plan_fn(*args, None, None, None, None), "slices_plan")
     out = {"why": _lib.SLICES_WHY[why.value], "n_desc": nd.value, "n_slices": ns.value,
            "padded_entries": pe.value}
     if why.value != 0 or not fill:
@@ -319,7 +349,7 @@ def slices_plan(A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, kernel: str = 
     rl = np.zeros(max(A.m, 1), np.uint8)
     pos = np.zeros(max(pe.value, 1), np.uint16)
     val = np.zeros(max(pe.value, 1), A.val.dtype)
-    check(L.hspmv_slices_plan(*args, _ptr(desc), _ptr(rl), _ptr(pos), _ptr(val)), "slices_plan")
+    check(plan_fn(*args, _ptr(desc), _ptr(rl), _ptr(pos), _ptr(val)), "slices_plan")
     out.update(desc=desc, len=rl[:A.m], pos=pos[:pe.value], val=val[:pe.value],
                n_desc=nd.value)
     return out
@@ -374,7 +404,12 @@ class SpMV:
     row kernels; 2 / "reproducible": bit-identical run to run, csort with
     fixed-point row sums allowed; 3 / "serial": every row summed in
     omp_spmv's order, y bit-identical to it; handle created with
-    hspmv_create_ex).
+    hspmv_create_ex).  ``vector_dtype``: the type of x, y, the products and the
+    sums (None: A's dtype).  ``np.float64`` over a float32 ``A`` is the mixed
+    handle (hspmv_create_mixed): the values are stored and streamed as float32,
+    y is what the float64 operator gives for the widened matrix; one device
+    only.  ``op.dtype`` is the vectors' type, ``op.value_dtype`` the stored
+    values'.
     """
 
     def __init__(self, A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, num_gpus: int = 1,
@@ -383,10 +418,11 @@ class SpMV:
                  xcd_remap: Optional[bool] = None, split_rows: bool = True, chunk_u: int = 0,
                  prefetch: Optional[bool] = None, xcd_chunk: int = 0, groups_per_wave: int = 0,
                  col16: Optional[bool] = None, devices: Optional[list] = None,
-                 options: Optional[dict] = None):
+                 options: Optional[dict] = None, vector_dtype=None):
         self.A = A
         self.maps = maps
-        self.dtype = A.val.dtype
+        self.value_dtype = A.val.dtype
+        self.dtype = A.val.dtype if vector_dtype is None else np.dtype(vector_dtype)
         flags = _KERNELS[kernel] | lanes_flag(lanes) | (FLAG_NONTEMPORAL if nontemporal else 0)
         flags |= remap_flag(xcd_remap, xcd_chunk) | _lib.groups_flag(groups_per_wave)
         flags |= _lib.col16_flag(col16)
@@ -400,6 +436,17 @@ class SpMV:
         cs = A.c_struct()
         ms = maps.c_struct() if maps is not None else None
         h = C.c_void_p()
+        if self.dtype != self.value_dtype:  # the mixed handle (any other pair: the library refuses)
+            if num_gpus != 1 and devices is None:
+                n = num_gpus if num_gpus > 0 else device_count()
+                devices = list(range(max(n, 1)))
+            opt = _lib.make_options(flags, options, device=0 if device is None else device,
+                                    stream=stream, devices=devices)
+            check(lib().hspmv_create_mixed(C.byref(h), C.byref(cs),
+                                           C.byref(ms) if ms is not None else None, C.byref(opt),
+                                           dtype_code(self.dtype)), "hspmv_create_mixed")
+            self._h = h
+            return
         if options:  # explicit planner choices: hspmv_create_ex
             if num_gpus != 1 and devices is None:
                 # num_gpus <= 0 means every visible GPU, as in hspmv_create
@@ -433,13 +480,16 @@ class SpMV:
                     split_rows: bool = True, chunk_u: int = 0,
                     prefetch: Optional[bool] = None, xcd_chunk: int = 0,
                     groups_per_wave: int = 0, col16: Optional[bool] = None,
-                    options: Optional[dict] = None) -> "SpMV":
+                    options: Optional[dict] = None, vector_dtype=None) -> "SpMV":
         """Handle over caller-owned DEVICE arrays (HSPMV_FLAG_DEVICE_PTRS):
-        csr_dev/maps_dev hold device pointers; A_meta supplies m, n, dtype."""
+        csr_dev/maps_dev hold device pointers; A_meta supplies m, n, dtype.
+        ``vector_dtype=np.float64`` over float32 values: the mixed handle (the
+        borrowed val is float32, bound x and y are float64)."""
         self = cls.__new__(cls)
         self.A = A_meta
         self.maps = None
-        self.dtype = A_meta.val.dtype
+        self.value_dtype = A_meta.val.dtype
+        self.dtype = A_meta.val.dtype if vector_dtype is None else np.dtype(vector_dtype)
         flags = (_KERNELS[kernel] | lanes_flag(lanes) | (FLAG_NONTEMPORAL if nontemporal else 0)
                  | FLAG_DEVICE_PTRS | remap_flag(xcd_remap, xcd_chunk)
                  | _lib.groups_flag(groups_per_wave) | _lib.col16_flag(col16)
@@ -447,9 +497,14 @@ class SpMV:
                  | (_lib.FLAG_PREFETCH if prefetch else 0))
         h = C.c_void_p()
         opt = _lib.make_options(flags, options, device=device, stream=stream)
-        check(lib().hspmv_create_ex(C.byref(h), C.byref(csr_dev),
-                                    C.byref(maps_dev) if maps_dev is not None else None,
-                                    C.byref(opt)), "hspmv_create_ex")
+        if self.dtype != self.value_dtype:
+            check(lib().hspmv_create_mixed(C.byref(h), C.byref(csr_dev),
+                                           C.byref(maps_dev) if maps_dev is not None else None,
+                                           C.byref(opt), dtype_code(self.dtype)), "hspmv_create_mixed")
+        else:
+            check(lib().hspmv_create_ex(C.byref(h), C.byref(csr_dev),
+                                        C.byref(maps_dev) if maps_dev is not None else None,
+                                        C.byref(opt)), "hspmv_create_ex")
         self._h = h
         return self
 
@@ -501,6 +556,12 @@ class SpMV:
         self.set_x(x)
         self.spmv()
         return self.get_y()
+
+    def dtypes(self):
+        """(value dtype, vector dtype) as the handle reports them (hspmv_get_dtypes)."""
+        a, b = C.c_int(), C.c_int()
+        check(lib().hspmv_get_dtypes(self._h, C.byref(a), C.byref(b)), "hspmv_get_dtypes")
+        return np.dtype(np_dtype(a.value)), np.dtype(np_dtype(b.value))
 
     def exchange(self):
         b, g = C.c_double(), C.c_double()

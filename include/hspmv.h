@@ -51,7 +51,10 @@ extern "C" {
  * (HSPMV_INFO_SIZE_1_0).  Also in 1.1 (appended, nothing moved):
  * hspmv_options.row_slices, hspmv_info.row_slices, hspmv_slices_plan;
  * hspmv_set_sweep, hspmv_block_order, hspmv_info.sweep; the multi-vector
- * operator hspmv_mm_* (hspmv_mm, hspmv_mm_info). */
+ * operator hspmv_mm_* (hspmv_mm, hspmv_mm_info); the mixed-precision handle
+ * (fp32 values under fp64 vectors): hspmv_create_mixed, hspmv_get_dtypes,
+ * hspmv_values_fit_f32, hspmv_slices_plan_vec -- functions only, no struct
+ * grew. */
 
 /* ---------------------------------------------------------------- status */
 #define HSPMV_OK 0
@@ -375,6 +378,65 @@ typedef struct {
 int hspmv_create_ex(hspmv_handle **h, const hspmv_csr *A, const hspmv_csr3_maps *maps,
                     const hspmv_options *opt);
 
+/* Mixed precision: the matrix values stored and streamed in A->dtype, while x,
+ * y, every product and every partial sum are vector_dtype.
+ *   vector_dtype == A->dtype              exactly hspmv_create_ex;
+ *   A->dtype HSPMV_F32, vector HSPMV_F64  the mixed handle;
+ *   anything else (fp64 values with fp32 vectors, an unknown code)
+ *                                          HSPMV_E_INVALID.
+ * A mixed handle reads 4 instead of 8 bytes per stored value; x given to
+ * hspmv_set_x / hspmv_bind_x_device and y from hspmv_get_y / bound with
+ * hspmv_bind_y_device are fp64, and with HSPMV_FLAG_DEVICE_PTRS the borrowed
+ * val is fp32.  Every other entry point works on it as on any handle.
+ * hspmv_info reports the mixed format: alg_bytes = nnz*(4+4) + (m+1)*4 +
+ * (x_entries + m)*8 (+ the map terms of hspmv_alg_bytes), format_bytes and
+ * device_bytes count 4-byte values, and hspmv_run's gbps_alg uses the same
+ * alg_bytes.
+ *
+ * Semantics and order contract.  Each value is widened to fp64 once, before
+ * its product (exact), so y is what the fp64 operator gives for the widened
+ * matrix, and the handle follows fp64's rules: rows of up to 40 nonzeros
+ * (not fp32's 56) are summed serially, bit-identical to omp_spmv in fp64 on
+ * the widened values and to an fp64 handle with the same options on the
+ * widened matrix, in every row kernel and plan; with deterministic = 3 every
+ * row is; longer rows are within the fp64 tolerance.  The split-row
+ * threshold, the x-dictionary LDS cap (8-byte x entries), chunk_u, the LDS
+ * padding and the other launch-shape picks are fp64's, because the LDS
+ * product buffers hold fp64.  The footprint rules -- the Infinity Cache
+ * residence test, the row slices' byte rule, the "streams from HBM" rule of
+ * the 16-bit columns and the sweep's AUTO rule -- are the same derivations
+ * with 4 value bytes and 8 vector bytes: footprint = nnz*(4+4) + m*(8+4) +
+ * n*8; slices: 64*padded*(4+2) + m + 8*(tasks+1) against nnz*(4+2) +
+ * 4*(m+1).  For equal dtypes every rule evaluates exactly as before.
+ * Kernels: STREAM, CSR3 (every plan), the row-slice kernel (value groups of
+ * four fp32 slots per 16-byte load, positions unchanged), VECTOR and the
+ * split-row kernels.  No column-sorted kernel: AUTO plans as under
+ * deterministic = 1 (row kernels, x slabs for irregular gathers), and
+ * HSPMV_KERNEL_CSORT or hspmv_options.csort = 1 returns HSPMV_E_INVALID;
+ * deterministic = 2 is accepted and runs the row kernels, which are
+ * reproducible.  placement_trials copies 4-byte values.
+ *
+ * Out of scope: multi-GPU shards (opt->n_devices > 1 returns
+ * HSPMV_E_INVALID), CSORT, hspmv_mm_* with mixed types, fp64 values with fp32
+ * vectors, bf16 / fp16 storage, automatic narrowing of an fp64 handle (the
+ * caller decides, with hspmv_values_fit_f32), and launch-shape rules tuned
+ * for the mixed kernels beyond the derivations above.
+ * The argument refusals (NULL, the dtype pair, n_devices, CSORT) are made
+ * before any device call. */
+int hspmv_create_mixed(hspmv_handle **h, const hspmv_csr *A, const hspmv_csr3_maps *maps,
+                       const hspmv_options *opt, int vector_dtype);
+/* The stored values' and the vectors' hspmv_dtype of a handle (equal for every
+ * handle but hspmv_create_mixed's).  Either pointer may be NULL. */
+int hspmv_get_dtypes(hspmv_handle *h, int *value_dtype, int *vector_dtype);
+/* Host only: 1 when every one of the nnz values of `dtype` converts to fp32
+ * and back to the same bits (an fp32 array trivially; a NaN when its round
+ * trip gives the same bits; -0.0 and +-inf do), so a mixed handle over the
+ * narrowed values computes the fp64 operator's y bit for bit; else 0, with
+ * *first_bad (may be NULL) = the first index that fails.  Negative
+ * (HSPMV_E_INVALID) for a NULL array with nnz > 0, nnz < 0 or an unknown
+ * dtype. */
+int hspmv_values_fit_f32(const void *val, int64_t nnz, int dtype, int64_t *first_bad);
+
 /* Upload A (and optional CSR-3 maps) to num_gpus devices (0 = all visible).
  * With num_gpus > 1 the rows are partitioned into nnz-balanced contiguous
  * ranges (on super-super-row boundaries when maps are given), x is
@@ -673,6 +735,15 @@ int hspmv_xdict_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, unsigned f
 int hspmv_slices_plan(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt,
                       int64_t *n_desc, int64_t *n_slices, int64_t *padded_entries, int32_t *why,
                       int32_t *desc, uint8_t *len, uint16_t *pos, void *val);
+/* hspmv_slices_plan for vectors of vector_dtype: with vector_dtype ==
+ * A->dtype exactly that; with fp32 A and HSPMV_F64 what hspmv_create_mixed
+ * builds -- val holds A's fp32 values in groups of four slots (G = 4), while
+ * the dictionaries (8-byte x entries), the serial bound (40) and so desc, len
+ * and pos are those of the widened fp64 matrix, and the byte and residence
+ * rules count 4-byte values.  Other pairs: HSPMV_E_INVALID. */
+int hspmv_slices_plan_vec(const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt,
+                          int vector_dtype, int64_t *n_desc, int64_t *n_slices, int64_t *padded_entries,
+                          int32_t *why, int32_t *desc, uint8_t *len, uint16_t *pos, void *val);
 /* The position stream a handle uploads for the row slices {desc, pos} of
  * hspmv_slices_plan (n_desc + 1 descriptor pairs, 64 * desc[2 n_desc]
  * positions).  *bits = 12 when every position is below 4096 (every block
