@@ -25,57 +25,37 @@ int check_handle(hspmv_handle *h) {
 // stored values' type).  hspmv_create_mixed passes HSPMV_F64 over fp32 values.
 int create_single(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps, int device,
                   void *stream, unsigned flags, const Tuning &tune, int vec_dtype = -1) {
-  ContigScope contig(tune);
   if (int rc0 = check_deterministic(flags, tune)) return rc0;
   const bool devptrs = (flags & HSPMV_FLAG_DEVICE_PTRS) != 0;
   if (!A) return set_error(HSPMV_E_INVALID, "matrix is NULL");
   if (vec_dtype < 0) vec_dtype = A->dtype;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return set_error(HSPMV_E_NODEV, "no HIP device available");
-  if (device < 0 || device >= ndev)
-    return set_error(HSPMV_E_NODEV, "device %d out of range (have %d)", device, ndev);
+  int rc;
+  if ((rc = check_device(device))) return rc;
+  // (an error return unwinds h: the shard's DevCtx frees what it holds)
   std::unique_ptr<hspmv_handle> h(new hspmv_handle());
   h->m = A->m; h->n = A->n; h->nnz = A->nnz; h->dtype = vec_dtype; h->val_dtype = A->dtype; h->flags = flags;
   h->shards.resize(1);
   Shard &s = h->shards[0];
-  s.device = device;
+  s.dev.device = device;
+  s.dev.contig = tune.contig == 1;
   s.tune = tune;
   s.dtype = vec_dtype;
   s.val_dtype = A->dtype;
-  int rc;
   if (!devptrs) {
     if ((rc = validate_host_csr(A, true))) return rc;
     if ((rc = validate_host_maps(maps, A->m))) return rc;
     if (maps && maps->n_ssr > 0) { h->n_ssr = maps->n_ssr; h->n_sr = maps->n_sr; }
-    if ((rc = upload_shard(s, A, maps, 0, A->m, 0, maps ? maps->n_ssr : 0, A->m, flags))) {
-      free_shard(s, false);
-      return rc;
-    }
+    if ((rc = upload_shard(s, A, maps, 0, A->m, 0, maps ? maps->n_ssr : 0, A->m, flags))) return rc;
   } else {
-    // Borrowed device arrays: validate what the kernels index with (row_ptr
-    // and the maps) on the host before the first launch.
-    h->borrowed = true;
-    if (A->m < 0 || A->n < 0 || A->nnz < 0 || A->m >= INT32_MAX || A->nnz >= INT32_MAX ||
-        (A->dtype != HSPMV_F32 && A->dtype != HSPMV_F64) || !A->row_ptr)
-      return set_error(HSPMV_E_INVALID, "bad device matrix description");
+    // Borrowed device arrays: validate what the kernels index with (row_ptr,
+    // the columns and the maps) on the host before the first launch.  They go
+    // into the views only, never into s.dev.
     HIP_TRY(hipSetDevice(device));
-    std::vector<int32_t> &rp = s.h_rp;
-    rp.resize((size_t)(A->m + 1));
-    HIP_TRY(hipMemcpy(rp.data(), A->row_ptr, 4 * (size_t)(A->m + 1), hipMemcpyDeviceToHost));
-    hspmv_csr view = *A;  // device col/val are only null-checked, never read here
-    view.row_ptr = rp.data();
-    if ((rc = validate_host_csr(&view, false)) != HSPMV_OK) return rc;
+    std::vector<int32_t> cols;  // host copy until the row tables are built
+    if ((rc = read_device_csr(A, s.h_rp, cols))) return rc;
     s.A.m = (int32_t)A->m; s.A.n = A->n; s.A.nnz = A->nnz;
     s.A.row_ptr = A->row_ptr; s.A.col_idx = A->col_idx; s.A.val = A->val;
-    std::vector<int32_t> cols((size_t)A->nnz);  // host copy until the row tables are built
-    {
-      if (A->nnz)
-        HIP_TRY(hipMemcpy(cols.data(), A->col_idx, 4 * (size_t)A->nnz, hipMemcpyDeviceToHost));
-      for (int32_t c : cols)
-        if (c < 0 || c >= A->n) return set_error(HSPMV_E_INVALID, "device col_idx %d out of [0, %lld)", c, (long long)A->n);
-      s.x_entries = count_distinct_cols(cols.data(), A->nnz, A->n);
-    }
+    s.x_entries = count_distinct_cols(cols.data(), A->nnz, A->n);
     if (maps && maps->n_ssr > 0) {
       std::vector<int32_t> &o = s.h_outer, &in = s.h_inner;
       o.resize((size_t)(maps->n_ssr + 1));
@@ -92,28 +72,15 @@ int create_single(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *
     // the values come back to the host too: the x slabs copy them slab-major
     std::vector<char> vals(dtype_size(A->dtype) * (size_t)A->nnz);
     if (A->nnz) HIP_TRY(hipMemcpy(vals.data(), A->val, vals.size(), hipMemcpyDeviceToHost));
-    // from here on the shard owns device memory: every error path frees it
-    if ((rc = build_row_tables(s, rp.data(), cols.data(), vals.data(), A->m, A->n, flags))) {
-      free_shard(s, true);
-      return rc;
-    }
+    if ((rc = build_row_tables(s, s.h_rp.data(), cols.data(), vals.data(), A->m, A->n, flags))) return rc;
     std::vector<char>().swap(vals);
     std::vector<int32_t>().swap(cols);
     const size_t sv = dtype_size(vec_dtype);
-    if ((rc = dev_alloc(&s.d_x, sv * (size_t)A->n, &s.bytes)) ||
-        (rc = dev_alloc(&s.d_y, sv * (size_t)A->m, &s.bytes))) {
-      free_shard(s, true);
+    if ((rc = s.dev.alloc(&s.d_x, sv * (size_t)A->n)) || (rc = s.dev.alloc(&s.d_y, sv * (size_t)A->m)))
       return rc;
-    }
   }
-  if ((rc = finish_shard(s, flags, stream))) {
-    free_shard(s, h->borrowed);
-    return rc;
-  }
-  if (!devptrs && (rc = place_shard(s, A->n))) {
-    free_shard(s, h->borrowed);
-    return rc;
-  }
+  if ((rc = finish_shard(s, flags, stream))) return rc;
+  if (!devptrs && (rc = place_shard(s, A->n))) return rc;
   (void)ncclGetVersion(&h->rccl_version);
   *hp = h.release();
   return HSPMV_OK;
@@ -137,14 +104,19 @@ bool shard_reverse(const hspmv_handle *h, const Shard &s) {
   return h->sweep_phase && shard_alternates(h, s);
 }
 
+// One SpMV of shard s on its stream (its device is the current one).
+int launch_shard(const hspmv_handle *h, Shard &s) {
+  hipError_t e = launch_spmv(s.A, s.dp, h->dtype, h->val_dtype, s.plan, s.x, s.y, s.dev.stream, shard_reverse(h, s));
+  if (e != hipSuccess)
+    return set_error(HSPMV_E_HIP, "SpMV launch on GPU %d failed: %s", s.dev.device, hipGetErrorString(e));
+  return HSPMV_OK;
+}
+
 int check_devices(const int *devices, int n, int *ndev_out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return set_error(HSPMV_E_NODEV, "no HIP device available");
-  *ndev_out = ndev;
+  int rc;
+  if ((rc = check_device(0, ndev_out))) return rc;  // any device at all, and how many
   for (int p = 0; devices && p < n; ++p)
-    if (devices[p] < 0 || devices[p] >= ndev)
-      return set_error(HSPMV_E_NODEV, "device %d out of range (have %d)", devices[p], ndev);
+    if ((rc = check_device(devices[p]))) return rc;
   return HSPMV_OK;
 }
 
@@ -280,15 +252,15 @@ int hspmv_set_x(hspmv_handle *h, const void *x_host) {
   if (!x_host && h->n > 0) return set_error(HSPMV_E_INVALID, "x is NULL");
   const size_t bytes = dtype_size(h->dtype) * (size_t)h->n;
   Shard &s0 = h->shards[0];
-  HIP_TRY(hipSetDevice(s0.device));
+  HIP_TRY(hipSetDevice(s0.dev.device));
   if (bytes) {
-    HIP_TRY(hipMemcpyAsync(s0.d_x, x_host, bytes, hipMemcpyHostToDevice, s0.stream));
-    HIP_TRY(hipStreamSynchronize(s0.stream));
+    HIP_TRY(hipMemcpyAsync(s0.d_x, x_host, bytes, hipMemcpyHostToDevice, s0.dev.stream));
+    HIP_TRY(hipStreamSynchronize(s0.dev.stream));
   }
   if ((rc = bcast_x(h))) return rc;
   for (auto &s : h->shards) {
-    HIP_TRY(hipSetDevice(s.device));
-    HIP_TRY(hipStreamSynchronize(s.stream));
+    HIP_TRY(hipSetDevice(s.dev.device));
+    HIP_TRY(hipStreamSynchronize(s.dev.stream));
     s.x = s.d_x;
   }
   h->x_set = true;
@@ -329,10 +301,8 @@ int hspmv_spmv(hspmv_handle *h) {
   if ((rc = check_handle(h))) return rc;
   if (!h->x_set) return set_error(HSPMV_E_STATE, "x not set (hspmv_set_x / hspmv_bind_x_device)");
   for (auto &s : h->shards) {
-    HIP_TRY(hipSetDevice(s.device));
-    hipError_t e = launch_spmv(s.A, s.dp, h->dtype, h->val_dtype, s.plan, s.x, s.y, s.stream, shard_reverse(h, s));
-    if (e != hipSuccess)
-      return set_error(HSPMV_E_HIP, "SpMV launch on GPU %d failed: %s", s.device, hipGetErrorString(e));
+    HIP_TRY(hipSetDevice(s.dev.device));
+    if ((rc = launch_shard(h, s))) return rc;
   }
   h->sweep_phase = !h->sweep_phase;
   return HSPMV_OK;
@@ -366,8 +336,8 @@ int hspmv_synchronize(hspmv_handle *h) {
   int rc;
   if ((rc = check_handle(h))) return rc;
   for (auto &s : h->shards) {
-    HIP_TRY(hipSetDevice(s.device));
-    HIP_TRY(hipStreamSynchronize(s.stream));
+    HIP_TRY(hipSetDevice(s.dev.device));
+    HIP_TRY(hipStreamSynchronize(s.dev.stream));
   }
   return HSPMV_OK;
 }
@@ -377,40 +347,20 @@ int hspmv_run(hspmv_handle *h, int warmup, int iters, hspmv_timing *out) {
   int rc;
   if ((rc = check_handle(h))) return rc;
   if (!out || iters < 1 || warmup < 0) return set_error(HSPMV_E_INVALID, "bad arguments");
-  for (int i = 0; i < warmup; ++i) {
-    if ((rc = hspmv_spmv(h))) return rc;
-    if ((rc = hspmv_synchronize(h))) return rc;
-  }
-  double tmin = 1e30, tmax = 0, tsum = 0, wmin = 1e30, wmax = 0, wsum = 0;
-  for (int i = 0; i < iters; ++i) {
-    auto tic = std::chrono::steady_clock::now();
-    for (auto &s : h->shards) {
-      HIP_TRY(hipSetDevice(s.device));
-      HIP_TRY(hipEventRecord(s.ev0, s.stream));
-      hipError_t e = launch_spmv(s.A, s.dp, h->dtype, h->val_dtype, s.plan, s.x, s.y, s.stream, shard_reverse(h, s));
-      if (e != hipSuccess)
-        return set_error(HSPMV_E_HIP, "SpMV launch failed: %s", hipGetErrorString(e));
-      HIP_TRY(hipEventRecord(s.ev1, s.stream));
-    }
-    h->sweep_phase = !h->sweep_phase;
-    double dev = 0.0;
-    for (auto &s : h->shards) {
-      HIP_TRY(hipSetDevice(s.device));
-      HIP_TRY(hipEventSynchronize(s.ev1));
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-      dev = std::max(dev, (double)ms * 1e-3);
-    }
-    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
-    tmin = std::min(tmin, dev); tmax = std::max(tmax, dev); tsum += dev;
-    wmin = std::min(wmin, wall); wmax = std::max(wmax, wall); wsum += wall;
-  }
-  memset(out, 0, sizeof(*out));
-  out->t_min = tmin; out->t_max = tmax; out->t_avg = tsum / iters;
-  out->wall_min = wmin; out->wall_max = wmax; out->wall_avg = wsum / iters;
+  // (as ever, only a warm-up launch asks for x)
+  if (warmup > 0 && !h->x_set) return set_error(HSPMV_E_STATE, "x not set (hspmv_set_x / hspmv_bind_x_device)");
+  std::vector<DevCtx *> devs;
+  for (auto &s : h->shards) devs.push_back(&s.dev);
+  // one SpMV of shard p; the direction flips once per iteration, after the last shard
+  auto enqueue = [&](size_t p) -> int {
+    const int e = launch_shard(h, h->shards[p]);
+    if (p + 1 == h->shards.size()) h->sweep_phase = !h->sweep_phase;
+    return e;
+  };
+  if ((rc = timed_run(devs, warmup, iters, enqueue, out))) return rc;
+  const double tmin = out->t_min;
   out->gflops = tmin > 0 ? 2.0 * (double)h->nnz / tmin * 1e-9 : 0.0;
   out->gbps_alg = tmin > 0 ? alg_bytes_of(h->m, h->x_entries(), h->nnz, h->dtype, h->val_dtype, h->n_ssr, h->n_sr) / tmin * 1e-9 : 0.0;
-  out->iters = iters;
   out->num_gpus = (int32_t)h->shards.size();
   return HSPMV_OK;
 }
@@ -423,16 +373,16 @@ int hspmv_get_y(hspmv_handle *h, void *y_host) {
   const size_t sv = dtype_size(h->dtype);
   if (!h->sharded) {
     Shard &s = h->shards[0];
-    HIP_TRY(hipSetDevice(s.device));
-    if (h->m) HIP_TRY(hipMemcpyAsync(y_host, s.y, sv * (size_t)h->m, hipMemcpyDeviceToHost, s.stream));
-    HIP_TRY(hipStreamSynchronize(s.stream));
+    HIP_TRY(hipSetDevice(s.dev.device));
+    if (h->m) HIP_TRY(hipMemcpyAsync(y_host, s.y, sv * (size_t)h->m, hipMemcpyDeviceToHost, s.dev.stream));
+    HIP_TRY(hipStreamSynchronize(s.dev.stream));
     return HSPMV_OK;
   }
   // RCCL all-gather of the padded shards, then unpad GPU 0's copy.
   if ((rc = gather_y(h))) return rc;
   if ((rc = hspmv_synchronize(h))) return rc;
   Shard &s0 = h->shards[0];
-  HIP_TRY(hipSetDevice(s0.device));
+  HIP_TRY(hipSetDevice(s0.dev.device));
   std::vector<char> full(sv * (size_t)(h->max_rows * (int64_t)h->shards.size()));
   HIP_TRY(hipMemcpy(full.data(), s0.d_yfull, full.size(), hipMemcpyDeviceToHost));
   for (size_t p = 0; p < h->shards.size(); ++p) {
@@ -481,7 +431,7 @@ static int fill_info(hspmv_handle *h, hspmv_info *out) {
   out->x_entries = h->x_entries();
   out->alg_bytes = alg_bytes_of(h->m, out->x_entries, h->nnz, h->dtype, h->val_dtype, h->n_ssr, h->n_sr);
   out->flops = 2.0 * (double)h->nnz;
-  for (auto &sh : h->shards) out->device_bytes += sh.bytes;
+  for (auto &sh : h->shards) out->device_bytes += sh.dev.bytes();
   out->chunk_u = s.plan.u;
   out->n_split_rows = s.dp.n_long;
   out->xcd_remap = s.plan.xcd_chunk;
@@ -558,7 +508,7 @@ int hspmv_diag_csort_trace(hspmv_handle *h, unsigned long long *out, int max_wg)
   const Shard &s = h->shards[0];
   if (s.plan.kernel != kCsort || !s.dp.cs.trace) return 0;
   const int n = std::min(max_wg, s.dp.cs.n_wg);
-  if (hipSetDevice(s.device) != hipSuccess || hipStreamSynchronize(s.stream) != hipSuccess ||
+  if (hipSetDevice(s.dev.device) != hipSuccess || hipStreamSynchronize(s.dev.stream) != hipSuccess ||
       hipMemcpy(out, s.dp.cs.trace, 8 * kCsortTraceSlots * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
     return 0;
   return n;
@@ -589,12 +539,11 @@ int hspmv_get_info_sized(hspmv_handle *h, hspmv_info *out, uint32_t out_size) {
 void hspmv_destroy(hspmv_handle *h) {
   if (!h) return;
   for (auto &s : h->shards) {
-    (void)hipSetDevice(s.device);
-    if (s.stream) (void)hipStreamSynchronize(s.stream);
+    (void)hipSetDevice(s.dev.device);
+    if (s.dev.stream) (void)hipStreamSynchronize(s.dev.stream);
   }
   for (auto c : h->comms) (void)ncclCommDestroy(c);
-  for (auto &s : h->shards) free_shard(s, h->borrowed);
-  delete h;
+  delete h;  // after the communicators: each shard's DevCtx frees what it holds
 }
 
 }  // extern "C"

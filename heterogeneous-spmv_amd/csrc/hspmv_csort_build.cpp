@@ -54,11 +54,11 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
                 int64_t n, int dtype, unsigned flags) {
   if (m == 0 || n == 0 || !val) return HSPMV_OK;
   int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s.device) != hipSuccess ||
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s.dev.device) != hipSuccess ||
       cus <= 0)
     cus = 256;
   int lds_max = 0;  // the row slots must fit one workgroup's LDS on THIS device
-  if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, s.device) != hipSuccess ||
+  if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, s.dev.device) != hipSuccess ||
       lds_max <= 0)
     return HSPMV_OK;
   // the kernel's static LDS (its chunk-queue head, 16 B with alignment)
@@ -534,25 +534,21 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
     for (int32_t r : lrow) mask[(size_t)r >> 5] |= 1u << (r & 31);
   }
   int rc;
+  // the tables go straight into the launch description (s.dev owns them)
+  DevCsort &c = s.csort;
+  c = DevCsort();
   auto up = [&](auto **d, const auto &h) -> int {
     using E = typename std::decay_t<decltype(h)>::value_type;
-    if (h.empty()) return dev_alloc(d, sizeof(E), &s.bytes);  // one element's room, as for a size of 1
-    return upload(s, d, h.data(), sizeof(E) * h.size());
+    if (h.empty()) return s.dev.alloc(d, sizeof(E));  // one element's room, as for a size of 1
+    return s.dev.upload(d, h.data(), sizeof(E) * h.size());
   };
-  if ((rc = up(&s.d_cs_blk_c, blk_c)) || (rc = up(&s.d_cs_blk_r, wg_rows)) ||
-      (rc = up(&s.d_cs_blk_v, blk_v)) || (rc = up(&s.d_cs_vslice, vslice)) || (rc = up(&s.d_cs_cbase, cbase)))
+  if ((rc = up(&c.blk_c, blk_c)) || (rc = up(&c.blk_r, wg_rows)) || (rc = up(&c.blk_v, blk_v)) ||
+      (rc = up(&c.vslice, vslice)) || (rc = up(&c.cbase, cbase)))
     return rc;
   if (dtype == HSPMV_F32) {
-    uint64_t *d = nullptr;
-    if ((rc = up(&d, rec))) return rc;
-    s.d_cs_ent = d;
+    if ((rc = up(&c.ent, rec))) return rc;
   } else {
-    uint32_t *di = nullptr;
-    double *dv = nullptr;
-    if ((rc = up(&di, idx))) return rc;
-    s.d_cs_ent = di;
-    if ((rc = up(&dv, val64))) return rc;
-    s.d_cs_val = dv;
+    if ((rc = up(&c.ent, idx)) || (rc = up(&c.val, val64))) return rc;
   }
   const bool direct = H == 1 && lrow.empty();
   // Row partials: fp32 for fp32 data (part32, the default since r06; the
@@ -566,26 +562,23 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   const bool part32 = dtype == HSPMV_F32 && !slot32 && tn.csort_part32 != 0;
   const int64_t part_bytes = part32 ? 4 : slot_bytes;
   if (!direct) {
-    if ((rc = dev_alloc(&s.d_cs_part, part_bytes * (size_t)H * (size_t)m, &s.bytes))) return rc;
-    if ((rc = dev_alloc(&s.d_cs_spart, slot_bytes * (size_t)std::max<int64_t>(n_slices, 1), &s.bytes)))
-      return rc;
+    if ((rc = s.dev.alloc(&c.part, part_bytes * (size_t)H * (size_t)m))) return rc;
+    if ((rc = s.dev.alloc(&c.spart, slot_bytes * (size_t)std::max<int64_t>(n_slices, 1)))) return rc;
   }
   if (!lrow.empty()) {
-    if ((rc = up(&s.d_cs_mask, mask)) || (rc = up(&s.d_cs_long_row, lrow)) || (rc = up(&s.d_cs_long_cs, lcs)))
+    if ((rc = up(&c.long_mask, mask)) || (rc = up(&c.long_row, lrow)) || (rc = up(&c.long_cs, lcs)))
       return rc;
   }
   int32_t n_xexp = 0;
   if (fixed) {  // the x-exponent pre-pass: one block per 8192 entries of x, at most kCsortXexpBlocks
-    if ((rc = up(&s.d_cs_rexp, rexp)) || (rc = up(&s.d_cs_sexp, sexp))) return rc;
+    if ((rc = up(&c.rexp, rexp)) || (rc = up(&c.sexp, sexp))) return rc;
     n_xexp = (int32_t)std::min<int64_t>(kCsortXexpBlocks,
                                         std::max<int64_t>(1, (n + kCsortXexpChunk - 1) / kCsortXexpChunk));
-    if ((rc = dev_alloc(&s.d_cs_xexp, 4 * (size_t)n_xexp, &s.bytes))) return rc;
+    if ((rc = s.dev.alloc(&c.xexp_part, 4 * (size_t)n_xexp))) return rc;
   }
   // (An in-launch combine -- write-through partials, an arrival counter per
   // row block, the last arriver adding the parts -- measured slower than
   // the finishing launch: C5 114.8 vs 107.3 us, profiles/r02s_*.)
-  DevCsort &c = s.csort;
-  c = DevCsort();
   c.n_wg = (int32_t)G;
   c.H = H;
   c.u = U;
@@ -600,9 +593,6 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   c.wide = wide;
   c.fin_rows = tn.csort_fin_rows;
   c.fixed = fixed;
-  c.rexp = s.d_cs_rexp;
-  c.sexp = s.d_cs_sexp;
-  c.xexp_part = s.d_cs_xexp;
   c.n_xexp = n_xexp;
   c.n_x = n;
   // waves claim chunks from the workgroup's LDS queue: one process, 7
@@ -611,9 +601,6 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   c.dyn = tn.csort_dyn != 0;
   c.m = m;
   c.lds_bytes = (int32_t)(slot_bytes * max_slots_used);
-  c.blk_c = s.d_cs_blk_c;
-  c.blk_r = s.d_cs_blk_r;
-  c.blk_v = s.d_cs_blk_v;
   c.row_blocks = (int32_t)NB;
   s.csort_seg_chunks = n_seg.load();
   if (stats) {
@@ -625,17 +612,7 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   }
   s.csort_chunks = tot_chunks;
   for (int h = 0; h < 4; ++h) s.csort_part_begin[h] = h < H ? pb[(size_t)h] : 0;
-  if (tn.csort_trace == 1 && (rc = dev_alloc(&s.d_cs_trace, 8 * kCsortTraceSlots * (size_t)G, &s.bytes))) return rc;
-  c.trace = s.d_cs_trace;
-  c.vslice = s.d_cs_vslice;
-  c.cbase = s.d_cs_cbase;
-  c.ent = s.d_cs_ent;
-  c.val = s.d_cs_val;
-  c.part = s.d_cs_part;
-  c.spart = s.d_cs_spart;
-  c.long_mask = s.d_cs_mask;
-  c.long_row = s.d_cs_long_row;
-  c.long_cs = s.d_cs_long_cs;
+  if (tn.csort_trace == 1 && (rc = s.dev.alloc(&c.trace, 8 * kCsortTraceSlots * (size_t)G))) return rc;
   // bytes moved: the entry stream + chunk bases + x (distinct columns) + the
   // partial sums written and read back + y
   const double xb = (double)s.x_entries * (double)sv;

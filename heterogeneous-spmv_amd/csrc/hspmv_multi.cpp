@@ -22,7 +22,6 @@ namespace hspmv {
 // unpadding are exercised on a one-GPU box.
 int create_sharded(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps,
                    const std::vector<int> &devs, unsigned flags, const Tuning &tune) {
-  ContigScope contig(tune);
   const int num_gpus = (int)devs.size();
   int rc;
   if ((rc = check_deterministic(flags, tune))) return rc;
@@ -50,29 +49,20 @@ int create_sharded(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps 
   h->max_rows = max_rows;
   h->shards.resize((size_t)num_gpus);
   const size_t sv = dtype_size(A->dtype);
-  auto cleanup = [&]() {
-    for (auto &s : h->shards) free_shard(s, false);
-  };
+  // (an error return unwinds h: every shard's DevCtx frees what it holds)
   for (int p = 0; p < num_gpus; ++p) {
     Shard &s = h->shards[p];
-    s.device = devs[(size_t)p];
+    s.dev.device = devs[(size_t)p];
+    s.dev.contig = tune.contig == 1;
     s.tune = tune;
     s.dtype = s.val_dtype = A->dtype;
     if ((rc = upload_shard(s, A, maps, splits[p], splits[p + 1], ssr_split[p], ssr_split[p + 1], 0,
-                           flags))) {
-      cleanup();
+                           flags)))
       return rc;
-    }
-    // y lives in this GPU's slot of a padded [P][max_rows] all-gather buffer
-    if ((rc = dev_alloc(&s.d_yfull, sv * (size_t)(max_rows * num_gpus), &s.bytes))) {
-      cleanup();
-      return rc;
-    }
+    // y is a view of this GPU's slot of a padded [P][max_rows] all-gather buffer
+    if ((rc = s.dev.alloc(&s.d_yfull, sv * (size_t)(max_rows * num_gpus)))) return rc;
     s.d_y = (char *)s.d_yfull + sv * (size_t)(max_rows * p);
-    if ((rc = finish_shard(s, flags, nullptr))) {
-      cleanup();
-      return rc;
-    }
+    if ((rc = finish_shard(s, flags, nullptr))) return rc;
   }
   std::vector<int> sorted(devs);
   std::sort(sorted.begin(), sorted.end());
@@ -82,7 +72,6 @@ int create_sharded(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps 
     std::vector<int> dl(devs);
     ncclResult_t r = ncclCommInitAll(h->comms.data(), num_gpus, dl.data());
     if (r != ncclSuccess) {
-      cleanup();
       h->comms.clear();
       return set_error(HSPMV_E_RCCL, "ncclCommInitAll: %s", ncclGetErrorString(r));
     }
@@ -103,32 +92,32 @@ static int copy_exchange(hspmv_handle *h, bool x_bcast) {
   int rc = HSPMV_OK;
   for (size_t p = 0; p < P && rc == HSPMV_OK; ++p) {
     Shard &s = h->shards[p];
-    if (hipSetDevice(s.device) != hipSuccess ||
+    if (hipSetDevice(s.dev.device) != hipSuccess ||
         hipEventCreateWithFlags(&done[p], hipEventDisableTiming) != hipSuccess ||
-        hipEventRecord(done[p], s.stream) != hipSuccess)
-      rc = set_error(HSPMV_E_HIP, "exchange: event setup on GPU %d failed", s.device);
+        hipEventRecord(done[p], s.dev.stream) != hipSuccess)
+      rc = set_error(HSPMV_E_HIP, "exchange: event setup on GPU %d failed", s.dev.device);
   }
   for (size_t q = 0; q < P && rc == HSPMV_OK; ++q) {
     Shard &d = h->shards[q];
-    if (hipSetDevice(d.device) != hipSuccess) {
-      rc = set_error(HSPMV_E_HIP, "hipSetDevice(%d) failed", d.device);
+    if (hipSetDevice(d.dev.device) != hipSuccess) {
+      rc = set_error(HSPMV_E_HIP, "hipSetDevice(%d) failed", d.dev.device);
       break;
     }
     for (size_t p = 0; p < P && rc == HSPMV_OK; ++p) {
       const Shard &src = h->shards[x_bcast ? 0 : p];
       if (x_bcast && q == 0) break;
-      if (hipStreamWaitEvent(d.stream, done[x_bcast ? 0 : p], 0) != hipSuccess) {
+      if (hipStreamWaitEvent(d.dev.stream, done[x_bcast ? 0 : p], 0) != hipSuccess) {
         rc = set_error(HSPMV_E_HIP, "exchange: stream wait failed");
         break;
       }
       hipError_t e;
       if (x_bcast) {
-        e = hipMemcpyPeerAsync(d.d_x, d.device, src.d_x, src.device, sv * (size_t)h->n, d.stream);
+        e = hipMemcpyPeerAsync(d.d_x, d.dev.device, src.d_x, src.dev.device, sv * (size_t)h->n, d.dev.stream);
       } else {
         char *dst = (char *)d.d_yfull + sv * (size_t)(h->max_rows * (int64_t)p);
         e = dst == src.d_y ? hipSuccess
-                           : hipMemcpyPeerAsync(dst, d.device, src.d_y, src.device,
-                                                sv * (size_t)src.A.m, d.stream);
+                           : hipMemcpyPeerAsync(dst, d.dev.device, src.d_y, src.dev.device,
+                                                sv * (size_t)src.A.m, d.dev.stream);
       }
       if (e != hipSuccess) rc = set_error(HSPMV_E_HIP, "exchange copy failed: %s", hipGetErrorString(e));
       if (x_bcast) break;
@@ -163,7 +152,7 @@ int bcast_x(hspmv_handle *h) {
   const ncclDataType_t dt = h->dtype == HSPMV_F64 ? ncclFloat64 : ncclFloat32;
   return rccl_group(h, "ncclBroadcast(x)", [&](size_t p) {
     Shard &s = h->shards[p];
-    return ncclBroadcast(h->shards[0].d_x, s.d_x, (size_t)h->n, dt, 0, h->comms[p], s.stream);
+    return ncclBroadcast(h->shards[0].d_x, s.d_x, (size_t)h->n, dt, 0, h->comms[p], s.dev.stream);
   });
 }
 
@@ -173,7 +162,7 @@ int gather_y(hspmv_handle *h) {
   const ncclDataType_t dt = h->dtype == HSPMV_F64 ? ncclFloat64 : ncclFloat32;
   return rccl_group(h, "ncclAllGather(y)", [&](size_t p) {
     Shard &s = h->shards[p];
-    return ncclAllGather(s.d_y, s.d_yfull, (size_t)h->max_rows, dt, h->comms[p], s.stream);
+    return ncclAllGather(s.d_y, s.d_yfull, (size_t)h->max_rows, dt, h->comms[p], s.dev.stream);
   });
 }
 

@@ -3,8 +3,10 @@
 //   hspmv_options.cpp      hspmv_options -> Tuning (+ diagnostic env knobs)
 //   hspmv_plan.cpp         plan_launch: the kernel and launch shape of a shard
 //                          (sees hspmv_internal.h only, not this header)
-//   hspmv_shard.cpp        device allocation, upload, launch-plan finish,
-//                          placement trials of one row-range shard
+//   hspmv_shard.cpp        DevCtx (the owner of device memory, streams and
+//                          events), upload, launch-plan finish and placement
+//                          trials of one row-range shard, the checks and the
+//                          timing loop the single- and multi-vector paths share
 //   hspmv_tables.cpp       host planner tables: 16-bit columns, wave tasks,
 //                          x windows, x slabs, split rows, CSR-3 SSR tasks
 //   hspmv_xdict.cpp        block x dictionaries (+ hspmv_xdict_plan), the
@@ -25,6 +27,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <thread>
 #include <vector>
 
@@ -41,11 +44,72 @@
 
 namespace hspmv {
 
-// One row-range shard on one GPU.
-struct Shard {
+// The owner of one device's side of a shard or an SpMM operator.  The
+// ownership rule of the whole runtime: what a DevCtx allocated or created it
+// frees -- early through release(), else in its destructor -- and nothing
+// else is ever freed.  Every other device pointer (Shard::d_*, DevCSR,
+// DevPlan, DevCsort, DevMM) is a view: into one of these allocations, or a
+// caller's borrowed array, which never enters a context.
+// alloc / upload / open / new_* expect `device` to be the current device.
+struct DevCtx {
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  hipStream_t stream = nullptr;  // launches: the caller's, or one this context created
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the timing pair (open)
+  // Tuning.contig (A/B, diagnostic builds): physically contiguous allocations
+  // (hipDeviceMallocContiguous; the plain allocation when that fails)
+  bool contig = false;
+
+  DevCtx() = default;
+  DevCtx(DevCtx &&o) noexcept;  // leaves o empty
+  DevCtx(const DevCtx &) = delete;
+  DevCtx &operator=(const DevCtx &) = delete;
+  // Frees every live allocation, owned event and owned stream on `device`;
+  // does not synchronise.
+  ~DevCtx();
+
+  // bytes of device memory (16 for a size of 0) into *p, recorded as owned
+  template <typename T>
+  int alloc(T **p, size_t bytes) {
+    void *q = nullptr;
+    const int rc = alloc_raw(&q, bytes);
+    *p = static_cast<T *>(q);
+    return rc;
+  }
+  // alloc + the host-to-device copy of the same bytes (none when bytes == 0)
+  template <typename T>
+  int upload(T **p, const void *src, size_t bytes) {
+    void *q = nullptr;
+    const int rc = upload_raw(&q, src, bytes);
+    *p = static_cast<T *>(q);
+    return rc;
+  }
+  // Frees one owned allocation now and forgets it; a pointer this context
+  // does not own (a borrowed array, nullptr) is left alone.
+  void release(const void *p);
+  int64_t bytes() const;  // the live allocations' recorded sizes (hspmv_info.device_bytes)
+  // The launch stream -- the caller's, or a new non-blocking one -- and ev0 / ev1.
+  int open(void *caller_stream);
+  // An extra owned non-blocking stream / event without timing (the serial
+  // long-row fork and join).
+  int new_stream(hipStream_t *st);
+  int new_event(hipEvent_t *ev, unsigned flags = hipEventDisableTiming);
+
+ private:
+  struct Block {
+    void *ptr;
+    size_t bytes;
+  };
+  std::vector<Block> blocks_;
+  std::vector<hipStream_t> streams_;
+  std::vector<hipEvent_t> events_;
+  int alloc_raw(void **p, size_t bytes);
+  int upload_raw(void **p, const void *src, size_t bytes);
+};
+
+// One row-range shard on one GPU: views, host tables and the plan; dev owns
+// the device side.
+struct Shard {
+  DevCtx dev;
   int64_t row0 = 0;  // first global row
   // dtype: x, y, the products and the sums; val_dtype: the stored values
   // (A.val, the slab and slice copies).  Equal, or HSPMV_F32 under HSPMV_F64
@@ -54,9 +118,9 @@ struct Shard {
   DevCSR A;          // device view (rows rebased to 0)
   LaunchPlan plan;
   double mean_rows_per_ssr = 0.0;
-  // owned device memory
+  // views of dev's allocations, carried from build_row_tables to build_plan_tables
   int32_t *d_rp = nullptr, *d_ci = nullptr, *d_outer = nullptr, *d_inner = nullptr;
-  uint16_t *d_c16 = nullptr;  // 16-bit column offsets (owned even for borrowed A)
+  uint16_t *d_c16 = nullptr;  // 16-bit column offsets
   int32_t *d_cbase = nullptr;
   uint64_t *d_cplanes = nullptr;
   int32_t *d_xwin = nullptr;         // STREAM x windows {lo, w} per 64-row group
@@ -74,25 +138,15 @@ struct Shard {
   uint16_t *d_sl_pos = nullptr;   // the position stream: 16-bit, or packed (sl_pos_bits = 12)
   int32_t *d_sl_ppre = nullptr;   // packed stream only: each slice's start in 128-byte units
   void *d_sl_val = nullptr;
-  int64_t sl_bytes = 0, sl_desc_n = 0, sl_padded = 0;  // device bytes, descriptors, sum of slice widths
+  int64_t sl_desc_n = 0, sl_padded = 0;  // descriptors, sum of slice widths
   int sl_pos_bits = 0;            // 0 no slices, else 12 or 16 (hspmv_slices_pack)
   int64_t sl_pos_bytes = 0;       // position bytes read per SpMV (the stream and d_sl_ppre)
-  bool owns_csr = false;             // d_rp / d_ci / d_val are this shard's own uploads
   int32_t *d_slab_rp = nullptr;      // x slabs (build_xslabs): per-slab row pointers,
   int32_t *d_slab_col = nullptr;     // slab-major columns and values
   void *d_slab_val = nullptr;
   int32_t n_slabs = 0;
-  // column-sorted row blocks (build_csort): owned tables, and the launch
-  // description they form (copied into dp.cs when the planner picks kCsort)
-  int32_t *d_cs_blk_c = nullptr, *d_cs_blk_r = nullptr, *d_cs_blk_v = nullptr,
-          *d_cs_vslice = nullptr, *d_cs_cbase = nullptr, *d_cs_long_row = nullptr,
-          *d_cs_long_cs = nullptr;
-  uint32_t *d_cs_mask = nullptr;
-  unsigned long long *d_cs_trace = nullptr;  // diagnostic builds: csort per-workgroup timestamps
-  void *d_cs_ent = nullptr, *d_cs_val = nullptr;
-  double *d_cs_part = nullptr, *d_cs_spart = nullptr;
-  int16_t *d_cs_rexp = nullptr, *d_cs_sexp = nullptr;  // reproducible csort: value scales
-  int32_t *d_cs_xexp = nullptr;                        // reproducible csort: x exponent pre-pass
+  // column-sorted row blocks (build_csort): the launch description of the
+  // tables (copied into dp.cs when the planner picks kCsort)
   DevCsort csort;
   double csort_format_bytes = 0.0;   // bytes one csort SpMV moves
   int64_t csort_chunks = 0, csort_seg_chunks = 0;  // chunks, and those stored slot-sorted
@@ -101,19 +155,15 @@ struct Shard {
   int c16g_shape = 0;                // group-base columns built for kStream groups / kCsr3 tasks
   std::vector<int32_t> h_xwin;       // built at upload (host columns at hand)
   std::vector<int32_t> h_xwin_t;     // the same per packed CSR-3 task
-  void *d_val = nullptr;
+  void *d_val = nullptr;   // own values (none for a borrowed matrix)
   void *d_x = nullptr;     // own x (n entries)
-  void *d_y = nullptr;     // own y (m_shard entries) -- or a slice of d_yfull
+  void *d_y = nullptr;     // own y (m_shard entries) -- or a view into d_yfull
   void *d_yfull = nullptr; // multi-GPU: padded all-gather buffer P*max_rows
   const void *x = nullptr; // x in use (own or bound)
   void *y = nullptr;       // y in use (own or bound)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipStream_t long_stream = nullptr;  // serial order: the long-row kernel's stream
-  hipEvent_t long_fork = nullptr, long_join = nullptr;
-  int64_t bytes = 0;
   int64_t x_entries = 0;   // distinct columns of this shard
   double c16_saved = 0.0;  // bytes per SpMV the 16-bit column offsets save
-  // planner tables (owned): CSR-3 wave tasks and split-row chunks
+  // planner tables: CSR-3 wave tasks and split-row chunks
   DevPlan dp;
   int32_t *d_task = nullptr, *d_long_row = nullptr, *d_long_cstart = nullptr,
           *d_chunk_k = nullptr;
@@ -137,7 +187,6 @@ struct hspmv_handle {
   int64_t n_ssr = 0, n_sr = 0;
   unsigned flags = 0;
   bool x_set = false;
-  bool borrowed = false;  // HSPMV_FLAG_DEVICE_PTRS: matrix arrays not owned
   int64_t max_rows = 0;   // multi-GPU padding for the y all-gather
   bool sharded = false;   // row-range partition (hspmv_create_sharded / num_gpus > 1)
   int64_t x_entries() const {
@@ -174,27 +223,20 @@ Tuning default_tuning();
 int check_deterministic(unsigned flags, const Tuning &t);
 
 // ---- hspmv_shard.cpp
-extern thread_local bool t_contig;
-// Sets the allocation mode of one handle creation (Tuning.contig) and
-// restores it on every return path.
-struct ContigScope {
-  explicit ContigScope(const Tuning &t) { t_contig = t.contig == 1; }
-  ~ContigScope() { t_contig = false; }
-};
-
-int dev_alloc_bytes(void **p, size_t bytes, int64_t *acc);
-template <typename T>
-inline int dev_alloc(T **p, size_t bytes, int64_t *acc) {
-  return dev_alloc_bytes((void **)p, bytes, acc);
-}
-// dev_alloc into a slot of s (accounted in s.bytes) + the host-to-device copy
-// of the same bytes (none when bytes == 0).
-int upload_bytes(Shard &s, void **slot, const void *src, size_t bytes);
-template <typename T>
-inline int upload(Shard &s, T **slot, const void *src, size_t bytes) {
-  return upload_bytes(s, (void **)slot, src, bytes);
-}
-void free_shard(Shard &s, bool borrowed);
+// HSPMV_E_NODEV unless `device` is one of the visible devices (*ndev of them).
+int check_device(int device, int *ndev = nullptr);
+// A borrowed device CSR (HSPMV_FLAG_DEVICE_PTRS) on the current device: the
+// description, then what the kernels index with -- the row pointers and the
+// columns, read back into rp and cols -- validated on the host before the
+// first launch.  The values are only null-checked.
+int read_device_csr(const hspmv_csr *A, std::vector<int32_t> &rp, std::vector<int32_t> &cols);
+// The reference timing protocol (hspmv_run, hspmv_mm_run): enqueue(p) puts
+// one iteration's work of devs[p] on its stream.  `warmup` iterations, each
+// synchronised, then `iters` timed ones: device time ev0 -> ev1 (the maximum
+// over devs) and wall time, min / max / mean into out's t_*, wall_* and
+// iters; everything else in *out is zeroed.
+int timed_run(const std::vector<DevCtx *> &devs, int warmup, int iters,
+              const std::function<int(size_t)> &enqueue, hspmv_timing *out);
 int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_t r0, int64_t r1,
                  int64_t ssr0, int64_t ssr1, int64_t y_rows_alloc, unsigned flags);
 int finish_shard(Shard &s, unsigned flags, void *stream);

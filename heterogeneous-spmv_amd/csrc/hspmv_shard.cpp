@@ -1,9 +1,11 @@
-// hspmv_shard.cpp -- one row-range shard: allocation, upload, plan finish, placement
+// hspmv_shard.cpp -- DevCtx (the owner of device memory, streams and events); one
+// row-range shard: upload, plan finish, placement; the shared checks and timing loop
 // (see hspmv_runtime.h for the split of the host runtime).
 #include <string.h>
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
@@ -14,78 +16,148 @@
 
 namespace hspmv {
 
-// Tuning.contig (A/B, diagnostic builds): physically contiguous device
-// allocations (hipDeviceMallocContiguous; plain hipMalloc when that fails).
-// Set for the duration of one handle creation (creation is not re-entrant per
-// thread).
-thread_local bool t_contig = false;
+DevCtx::DevCtx(DevCtx &&o) noexcept
+    : device(o.device), stream(o.stream), ev0(o.ev0), ev1(o.ev1), contig(o.contig),
+      blocks_(std::move(o.blocks_)), streams_(std::move(o.streams_)), events_(std::move(o.events_)) {
+  o.stream = nullptr;
+  o.ev0 = o.ev1 = nullptr;
+}
 
-int dev_alloc_bytes(void **p, size_t bytes, int64_t *acc) {
+DevCtx::~DevCtx() {
+  if (blocks_.empty() && streams_.empty() && events_.empty()) return;  // owns nothing: no HIP call
+  (void)hipSetDevice(device);
+  for (const Block &b : blocks_) (void)hipFree(b.ptr);
+  for (hipEvent_t e : events_) (void)hipEventDestroy(e);
+  for (hipStream_t st : streams_) (void)hipStreamDestroy(st);
+}
+
+int DevCtx::alloc_raw(void **p, size_t bytes) {
   *p = nullptr;
   if (bytes == 0) bytes = 16;
   hipError_t e = hipErrorMemoryAllocation;
-  if (t_contig) {
+  if (contig) {
     e = hipExtMallocWithFlags(p, bytes, hipDeviceMallocContiguous);
     if (e != hipSuccess) (void)hipGetLastError();
   }
   if (e != hipSuccess) e = hipMalloc(p, bytes);
   if (e != hipSuccess)
     return set_error(HSPMV_E_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  *acc += (int64_t)bytes;
+  blocks_.push_back({*p, bytes});
   return HSPMV_OK;
 }
 
-int upload_bytes(Shard &s, void **slot, const void *src, size_t bytes) {
-  const int rc = dev_alloc_bytes(slot, bytes, &s.bytes);
+int DevCtx::upload_raw(void **p, const void *src, size_t bytes) {
+  const int rc = alloc_raw(p, bytes);
   if (rc) return rc;
-  if (bytes) HIP_TRY(hipMemcpy(*slot, src, bytes, hipMemcpyHostToDevice));
+  if (bytes) HIP_TRY(hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice));
   return HSPMV_OK;
 }
 
-void free_shard(Shard &s, bool borrowed) {
-  (void)hipSetDevice(s.device);
-  if (!borrowed) {
-    (void)hipFree(s.d_rp);
-    (void)hipFree(s.d_ci);
-    (void)hipFree(s.d_val);
-    (void)hipFree(s.d_outer);
-    (void)hipFree(s.d_inner);
+void DevCtx::release(const void *p) {
+  for (size_t i = 0; p && i < blocks_.size(); ++i)
+    if (blocks_[i].ptr == p) {
+      (void)hipFree(blocks_[i].ptr);
+      blocks_.erase(blocks_.begin() + (ptrdiff_t)i);
+      return;
+    }
+}
+
+int64_t DevCtx::bytes() const {
+  int64_t t = 0;
+  for (const Block &b : blocks_) t += (int64_t)b.bytes;
+  return t;
+}
+
+int DevCtx::new_stream(hipStream_t *st) {
+  HIP_TRY(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+  streams_.push_back(*st);
+  return HSPMV_OK;
+}
+
+int DevCtx::new_event(hipEvent_t *ev, unsigned flags) {
+  HIP_TRY(hipEventCreateWithFlags(ev, flags));
+  events_.push_back(*ev);
+  return HSPMV_OK;
+}
+
+int DevCtx::open(void *caller_stream) {
+  int rc;
+  if (caller_stream)
+    stream = (hipStream_t)caller_stream;
+  else if ((rc = new_stream(&stream)))
+    return rc;
+  if ((rc = new_event(&ev0, hipEventDefault)) || (rc = new_event(&ev1, hipEventDefault))) return rc;
+  return HSPMV_OK;
+}
+
+int check_device(int device, int *ndev_out) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    return set_error(HSPMV_E_NODEV, "no HIP device available");
+  if (ndev_out) *ndev_out = ndev;
+  if (device < 0 || device >= ndev)
+    return set_error(HSPMV_E_NODEV, "device %d out of range (have %d)", device, ndev);
+  return HSPMV_OK;
+}
+
+int read_device_csr(const hspmv_csr *A, std::vector<int32_t> &rp, std::vector<int32_t> &cols) {
+  if (A->m < 0 || A->n < 0 || A->nnz < 0 || A->m >= INT32_MAX || A->nnz >= INT32_MAX ||
+      (A->dtype != HSPMV_F32 && A->dtype != HSPMV_F64) || !A->row_ptr)
+    return set_error(HSPMV_E_INVALID, "bad device matrix description");
+  rp.resize((size_t)(A->m + 1));
+  HIP_TRY(hipMemcpy(rp.data(), A->row_ptr, 4 * rp.size(), hipMemcpyDeviceToHost));
+  hspmv_csr view = *A;  // device col/val are only null-checked, never read here
+  view.row_ptr = rp.data();
+  int rc;
+  if ((rc = validate_host_csr(&view, false))) return rc;
+  cols.resize((size_t)A->nnz);
+  if (A->nnz) HIP_TRY(hipMemcpy(cols.data(), A->col_idx, 4 * cols.size(), hipMemcpyDeviceToHost));
+  for (int32_t c : cols)
+    if (c < 0 || c >= A->n)
+      return set_error(HSPMV_E_INVALID, "device col_idx %d out of [0, %lld)", c, (long long)A->n);
+  return HSPMV_OK;
+}
+
+int timed_run(const std::vector<DevCtx *> &devs, int warmup, int iters,
+              const std::function<int(size_t)> &enqueue, hspmv_timing *out) {
+  int rc;
+  for (int i = 0; i < warmup; ++i) {
+    for (size_t p = 0; p < devs.size(); ++p) {
+      HIP_TRY(hipSetDevice(devs[p]->device));
+      if ((rc = enqueue(p))) return rc;
+    }
+    for (DevCtx *d : devs) {
+      HIP_TRY(hipSetDevice(d->device));
+      HIP_TRY(hipStreamSynchronize(d->stream));
+    }
   }
-  (void)hipFree(s.d_c16);
-  (void)hipFree(s.d_cbase);
-  (void)hipFree(s.d_cplanes);
-  (void)hipFree(s.d_xwin);
-  (void)hipFree(s.d_xd_blk);
-  (void)hipFree(s.d_xd_runs);
-  (void)hipFree(s.d_sl_desc);
-  (void)hipFree(s.d_sl_len);
-  (void)hipFree(s.d_sl_pos);
-  (void)hipFree(s.d_sl_ppre);
-  (void)hipFree(s.d_sl_val);
-  (void)hipFree(s.d_slab_rp);
-  (void)hipFree(s.d_slab_col);
-  (void)hipFree(s.d_slab_val);
-  for (void *p : {(void *)s.d_cs_blk_c, (void *)s.d_cs_blk_r, (void *)s.d_cs_blk_v,
-                  (void *)s.d_cs_vslice, (void *)s.d_cs_cbase, (void *)s.d_cs_long_row,
-                  (void *)s.d_cs_long_cs, (void *)s.d_cs_mask, s.d_cs_ent, s.d_cs_val,
-                  (void *)s.d_cs_part, (void *)s.d_cs_spart, (void *)s.d_cs_trace, (void *)s.d_cs_rexp,
-                  (void *)s.d_cs_sexp, (void *)s.d_cs_xexp})
-    (void)hipFree(p);
-  (void)hipFree(s.d_task);
-  (void)hipFree(s.d_long_row);
-  (void)hipFree(s.d_long_cstart);
-  (void)hipFree(s.d_chunk_k);
-  (void)hipFree(s.d_partials);
-  (void)hipFree(s.d_x);
-  if (!s.d_yfull) (void)hipFree(s.d_y);
-  (void)hipFree(s.d_yfull);
-  if (s.ev0) (void)hipEventDestroy(s.ev0);
-  if (s.ev1) (void)hipEventDestroy(s.ev1);
-  if (s.own_stream && s.stream) (void)hipStreamDestroy(s.stream);
-  if (s.long_fork) (void)hipEventDestroy(s.long_fork);
-  if (s.long_join) (void)hipEventDestroy(s.long_join);
-  if (s.long_stream) (void)hipStreamDestroy(s.long_stream);
-  s = Shard();
+  double tmin = 1e30, tmax = 0, tsum = 0, wmin = 1e30, wmax = 0, wsum = 0;
+  for (int i = 0; i < iters; ++i) {
+    auto tic = std::chrono::steady_clock::now();
+    for (size_t p = 0; p < devs.size(); ++p) {
+      DevCtx *d = devs[p];
+      HIP_TRY(hipSetDevice(d->device));
+      HIP_TRY(hipEventRecord(d->ev0, d->stream));
+      if ((rc = enqueue(p))) return rc;
+      HIP_TRY(hipEventRecord(d->ev1, d->stream));
+    }
+    double dev = 0.0;
+    for (DevCtx *d : devs) {
+      HIP_TRY(hipSetDevice(d->device));
+      HIP_TRY(hipEventSynchronize(d->ev1));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+      dev = std::max(dev, (double)ms * 1e-3);
+    }
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
+    tmin = std::min(tmin, dev); tmax = std::max(tmax, dev); tsum += dev;
+    wmin = std::min(wmin, wall); wmax = std::max(wmax, wall); wsum += wall;
+  }
+  memset(out, 0, sizeof(*out));
+  out->t_min = tmin; out->t_max = tmax; out->t_avg = tsum / iters;
+  out->wall_min = wmin; out->wall_max = wmax; out->wall_avg = wsum / iters;
+  out->iters = iters;
+  return HSPMV_OK;
 }
 
 // Uploads rows [r0, r1) of A (and the matching slice of the maps) to shard s.
@@ -95,18 +167,18 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
   const int64_t m = r1 - r0;
   const int64_t k0 = A->row_ptr[r0], k1 = A->row_ptr[r1];
   const int64_t nnz = k1 - k0;
-  HIP_TRY(hipSetDevice(s.device));
+  HIP_TRY(hipSetDevice(s.dev.device));
   s.row0 = r0;
   int rc;
   std::vector<int32_t> &rp = s.h_rp;
   rp.resize((size_t)(m + 1));
   for (int64_t i = 0; i <= m; ++i) rp[i] = (int32_t)(A->row_ptr[r0 + i] - k0);
-  if ((rc = upload(s, &s.d_rp, rp.data(), 4 * (size_t)(m + 1)))) return rc;
-  if ((rc = upload(s, &s.d_ci, A->col_idx + k0, 4 * (size_t)nnz))) return rc;
-  if ((rc = upload(s, &s.d_val, (const char *)A->val + sv * k0, sv * (size_t)nnz))) return rc;
-  if ((rc = dev_alloc(&s.d_x, sx * (size_t)A->n, &s.bytes))) return rc;
+  if ((rc = s.dev.upload(&s.d_rp, rp.data(), 4 * (size_t)(m + 1)))) return rc;
+  if ((rc = s.dev.upload(&s.d_ci, A->col_idx + k0, 4 * (size_t)nnz))) return rc;
+  if ((rc = s.dev.upload(&s.d_val, (const char *)A->val + sv * k0, sv * (size_t)nnz))) return rc;
+  if ((rc = s.dev.alloc(&s.d_x, sx * (size_t)A->n))) return rc;
   if (y_rows_alloc > 0) {
-    if ((rc = dev_alloc(&s.d_y, sx * (size_t)y_rows_alloc, &s.bytes))) return rc;
+    if ((rc = s.dev.alloc(&s.d_y, sx * (size_t)y_rows_alloc))) return rc;
   }
   s.x_entries = count_distinct_cols(A->col_idx + k0, nnz, A->n);
   s.A.m = (int32_t)m;
@@ -115,7 +187,6 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
   s.A.row_ptr = s.d_rp;
   s.A.col_idx = s.d_ci;
   s.A.val = s.d_val;
-  s.owns_csr = true;
   if (mp && mp->n_ssr > 0) {
     const int64_t nssr = ssr1 - ssr0;
     const int64_t sr0 = mp->outer[ssr0], sr1 = mp->outer[ssr1];
@@ -125,8 +196,8 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
     in.resize((size_t)(nsr + 1));
     for (int64_t i = 0; i <= nssr; ++i) o[i] = (int32_t)(mp->outer[ssr0 + i] - sr0);
     for (int64_t i = 0; i <= nsr; ++i) in[i] = (int32_t)(mp->inner[sr0 + i] - r0);
-    if ((rc = upload(s, &s.d_outer, o.data(), 4 * o.size()))) return rc;
-    if ((rc = upload(s, &s.d_inner, in.data(), 4 * in.size()))) return rc;
+    if ((rc = s.dev.upload(&s.d_outer, o.data(), 4 * o.size()))) return rc;
+    if ((rc = s.dev.upload(&s.d_inner, in.data(), 4 * in.size()))) return rc;
     s.A.n_ssr = (int32_t)nssr;
     s.A.n_sr = (int32_t)nsr;
     s.A.outer = s.d_outer;
@@ -137,23 +208,15 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
 }
 
 int finish_shard(Shard &s, unsigned flags, void *stream) {
-  HIP_TRY(hipSetDevice(s.device));
-  if (stream) {
-    s.stream = (hipStream_t)stream;
-    s.own_stream = false;
-  } else {
-    HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    s.own_stream = true;
-  }
-  HIP_TRY(hipEventCreate(&s.ev0));
-  HIP_TRY(hipEventCreate(&s.ev1));
+  HIP_TRY(hipSetDevice(s.dev.device));
+  int rc;
+  if ((rc = s.dev.open(stream))) return rc;
   // CSR-3 block size from the mean rows per super-super-row (sizing on the
   // 90th percentile doubled C3's waves for a 7-12 % loss, r01_ab_csr3_tasks)
   const double ssr_rows = s.mean_rows_per_ssr;
   s.plan = plan_launch(s.A, s.dtype, s.val_dtype, flags, ssr_rows,
                        s.h_tasks.empty() ? 0 : (int64_t)s.h_tasks.size() - 1, s.tune);
-  int rc = build_plan_tables(s, flags);
-  if (rc) return rc;
+  if ((rc = build_plan_tables(s, flags))) return rc;
   s.x = s.d_x;
   s.y = s.d_y;
   std::vector<int32_t>().swap(s.h_rp);
@@ -166,15 +229,15 @@ int finish_shard(Shard &s, unsigned flags, void *stream) {
 // the best of 3 event-timed runs of 5 launches.  < 0 on a launch error.
 static double time_shard(Shard &s) {
   for (int i = 0; i < 2; ++i)
-    if (launch_spmv(s.A, s.dp, s.dtype, s.val_dtype, s.plan, s.x, s.y, s.stream) != hipSuccess) return -1.0;
+    if (launch_spmv(s.A, s.dp, s.dtype, s.val_dtype, s.plan, s.x, s.y, s.dev.stream) != hipSuccess) return -1.0;
   double best = 1e30;
   for (int r = 0; r < 3; ++r) {
-    if (hipEventRecord(s.ev0, s.stream) != hipSuccess) return -1.0;
+    if (hipEventRecord(s.dev.ev0, s.dev.stream) != hipSuccess) return -1.0;
     for (int i = 0; i < 5; ++i)
-      if (launch_spmv(s.A, s.dp, s.dtype, s.val_dtype, s.plan, s.x, s.y, s.stream) != hipSuccess) return -1.0;
+      if (launch_spmv(s.A, s.dp, s.dtype, s.val_dtype, s.plan, s.x, s.y, s.dev.stream) != hipSuccess) return -1.0;
     float ms = 0.0f;
-    if (hipEventRecord(s.ev1, s.stream) != hipSuccess || hipEventSynchronize(s.ev1) != hipSuccess ||
-        hipEventElapsedTime(&ms, s.ev0, s.ev1) != hipSuccess)
+    if (hipEventRecord(s.dev.ev1, s.dev.stream) != hipSuccess || hipEventSynchronize(s.dev.ev1) != hipSuccess ||
+        hipEventElapsedTime(&ms, s.dev.ev0, s.dev.ev1) != hipSuccess)
       return -1.0;
     best = std::min(best, 1000.0 * (double)ms / 5.0);
   }
@@ -189,7 +252,7 @@ static double time_shard(Shard &s) {
 // positions/offsets or 32-bit columns), values, x and y -- are copied into
 // trials-1 fresh allocations in turn (all held until the end, so each lands
 // elsewhere), every set is timed over a few SpMVs, and the fastest is kept;
-// the others are freed.  The kernel, its tables and every bit of y are the
+// the others are released.  The kernel, its tables and every bit of y are the
 // same for all sets.  Single-GPU handles with owned arrays whose row kernel
 // (STREAM / CSR3) streams from HBM; Tuning.placement_trials = K sets the number of sets
 // (0 or 1 = off); memory for the extra sets must be free, else fewer are
@@ -233,7 +296,7 @@ int place_shard(Shard &s, int64_t n) {
     s.x = s.d_x;
     s.y = s.d_y;
   };
-  HIP_TRY(hipMemsetAsync(s.d_x, 0, sv * (size_t)n, s.stream));
+  HIP_TRY(hipMemsetAsync(s.d_x, 0, sv * (size_t)n, s.dev.stream));
   std::vector<std::vector<void *>> sets(1);
   for (auto &a : arrs) sets[0].push_back(*a.slot);
   s.place_us.assign(1, time_shard(s));
@@ -243,17 +306,18 @@ int place_shard(Shard &s, int64_t n) {
     std::vector<void *> set;
     for (auto &a : arrs) {
       void *p = nullptr;
-      if (hipMalloc(&p, a.bytes) != hipSuccess) break;
+      if (s.dev.alloc(&p, a.bytes) != HSPMV_OK) break;
       set.push_back(p);
-      if (hipMemcpyAsync(p, *a.slot, a.bytes, hipMemcpyDeviceToDevice, s.stream) != hipSuccess) {
+      if (hipMemcpyAsync(p, *a.slot, a.bytes, hipMemcpyDeviceToDevice, s.dev.stream) != hipSuccess) {
         rc = set_error(HSPMV_E_HIP, "placement trial: copy failed");
         break;
       }
     }
     if (rc != HSPMV_OK || set.size() != arrs.size()) {  // out of memory or a failed copy: stop
-      (void)hipStreamSynchronize(s.stream);
-      for (void *p : set) (void)hipFree(p);
+      (void)hipStreamSynchronize(s.dev.stream);
+      for (void *p : set) s.dev.release(p);
       (void)hipGetLastError();
+      if (rc == HSPMV_OK) clear_error();  // out of memory only ends the trials
       break;
     }
     for (size_t i = 0; i < arrs.size(); ++i) *arrs[i].slot = set[i];
@@ -263,13 +327,13 @@ int place_shard(Shard &s, int64_t n) {
     s.place_us.push_back(t);
     if (t < 0) rc = set_error(HSPMV_E_HIP, "placement trial: launch failed");
   }
-  HIP_TRY(hipStreamSynchronize(s.stream));
+  HIP_TRY(hipStreamSynchronize(s.dev.stream));
   int pick = 0;
   for (int k = 1; k < (int)sets.size(); ++k)
     if (s.place_us[(size_t)k] >= 0 && s.place_us[(size_t)k] < s.place_us[(size_t)pick]) pick = k;
   for (int k = 0; k < (int)sets.size(); ++k)
     if (k != pick)
-      for (void *p : sets[(size_t)k]) (void)hipFree(p);
+      for (void *p : sets[(size_t)k]) s.dev.release(p);
   for (size_t i = 0; i < arrs.size(); ++i) *arrs[i].slot = sets[(size_t)pick][i];
   point();
   s.place_pick = pick;

@@ -219,15 +219,14 @@ int upload_slices(Shard &s, const SlicePlan &P) {
       return rc;
     pos_bytes = packed.size();
     table_bytes = 4 * prefix.size();
-    if ((rc = upload(s, &s.d_sl_pos, packed.data(), pos_bytes))) return rc;
-    if ((rc = upload(s, &s.d_sl_ppre, prefix.data(), table_bytes))) return rc;
-  } else if ((rc = upload(s, &s.d_sl_pos, P.pos.data(), pos_bytes))) {  // the plan's stream as it is
+    if ((rc = s.dev.upload(&s.d_sl_pos, packed.data(), pos_bytes))) return rc;
+    if ((rc = s.dev.upload(&s.d_sl_ppre, prefix.data(), table_bytes))) return rc;
+  } else if ((rc = s.dev.upload(&s.d_sl_pos, P.pos.data(), pos_bytes))) {  // the plan's stream as it is
     return rc;
   }
-  if ((rc = upload(s, &s.d_sl_desc, P.desc.data(), 4 * P.desc.size()))) return rc;
-  if ((rc = upload(s, &s.d_sl_len, P.len.data(), P.len.size()))) return rc;
-  if ((rc = upload(s, &s.d_sl_val, P.val.data(), P.val.size()))) return rc;
-  s.sl_bytes = (int64_t)(4 * P.desc.size() + P.len.size() + pos_bytes + table_bytes + P.val.size());
+  if ((rc = s.dev.upload(&s.d_sl_desc, P.desc.data(), 4 * P.desc.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_sl_len, P.len.data(), P.len.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_sl_val, P.val.data(), P.val.size()))) return rc;
   s.sl_desc_n = nd;
   s.sl_padded = P.padded;
   s.sl_pos_bits = bits;
@@ -237,14 +236,12 @@ int upload_slices(Shard &s, const SlicePlan &P) {
 
 void drop_slices(Shard &s) {
   for (void *p : {(void *)s.d_sl_desc, (void *)s.d_sl_len, (void *)s.d_sl_pos, (void *)s.d_sl_ppre, s.d_sl_val})
-    if (p) (void)hipFree(p);
-  if (s.d_sl_desc) s.bytes -= s.sl_bytes;
+    s.dev.release(p);
   s.d_sl_desc = nullptr;
   s.d_sl_len = nullptr;
   s.d_sl_pos = nullptr;
   s.d_sl_ppre = nullptr;
   s.d_sl_val = nullptr;
-  s.sl_bytes = 0;
   s.sl_pos_bits = 0;
   s.A.has_slices = false;
 }

@@ -79,9 +79,9 @@ int build_col16(Shard &s, const int32_t *col, int64_t nnz, int64_t m, int64_t n,
     }
   });
   int rc;
-  if ((rc = upload(s, &s.d_c16, off.data(), 2 * off.size()))) return rc;
-  if ((rc = upload(s, &s.d_cbase, base.data(), 4 * base.size()))) return rc;
-  if (planes && (rc = upload(s, &s.d_cplanes, pl.data(), 8 * pl.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_c16, off.data(), 2 * off.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_cbase, base.data(), 4 * base.size()))) return rc;
+  if (planes && (rc = s.dev.upload(&s.d_cplanes, pl.data(), 8 * pl.size()))) return rc;
   s.A.col16 = s.d_c16;
   s.A.cbase = s.d_cbase;
   s.A.cplanes = s.d_cplanes;
@@ -151,8 +151,8 @@ int build_col16g(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int
     }
   });
   int rc;
-  if ((rc = upload(s, &s.d_c16, off.data(), 2 * off.size()))) return rc;
-  if ((rc = upload(s, &s.d_cbase, base.data(), 4 * base.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_c16, off.data(), 2 * off.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_cbase, base.data(), 4 * base.size()))) return rc;
   int bits = 0;
   while (bits < 31 && (int64_t(1) << bits) <= maxspan) ++bits;
   s.A.col_span_bits = std::max(1, bits);
@@ -594,9 +594,9 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
     }
   });
   int rc;
-  if ((rc = upload(s, &s.d_slab_rp, srp.data(), 4 * srp.size()))) return rc;
-  if ((rc = upload(s, &s.d_slab_col, scol.data(), 4 * scol.size()))) return rc;
-  if ((rc = upload(s, &s.d_slab_val, svals.data(), svals.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_slab_rp, srp.data(), 4 * srp.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_slab_col, scol.data(), 4 * scol.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_slab_val, svals.data(), svals.size()))) return rc;
   s.n_slabs = B;
   return HSPMV_OK;
 }
@@ -750,26 +750,23 @@ int build_plan_tables(Shard &s, unsigned flags) {
     if (!lrow.empty() && s.dp.serial_max == INT32_MAX) {  // serial order: one workgroup per row
       int rc;
       const int64_t nl = (int64_t)lrow.size();
-      if ((rc = upload(s, &s.d_long_row, lrow.data(), 4 * lrow.size()))) return rc;
-      if ((rc = dev_alloc(&s.d_partials, dtype_size(dtype) * (size_t)nl, &s.bytes))) return rc;
+      if ((rc = s.dev.upload(&s.d_long_row, lrow.data(), 4 * lrow.size()))) return rc;
+      if ((rc = s.dev.alloc(&s.d_partials, dtype_size(dtype) * (size_t)nl))) return rc;
       s.dp.partials = s.d_partials;  // the rows' sums, scattered into y after the row kernel
       s.dp.long_t = kLongRow;
       s.dp.n_long = (int32_t)nl;
       s.dp.long_row = s.d_long_row;
       s.dp.long_serial = true;
-      HIP_TRY(hipStreamCreateWithFlags(&s.long_stream, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&s.long_fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&s.long_join, hipEventDisableTiming));
-      s.dp.long_stream = s.long_stream;
-      s.dp.long_fork = s.long_fork;
-      s.dp.long_join = s.long_join;
+      if ((rc = s.dev.new_stream(&s.dp.long_stream)) || (rc = s.dev.new_event(&s.dp.long_fork)) ||
+          (rc = s.dev.new_event(&s.dp.long_join)))
+        return rc;
     } else if (!lrow.empty()) {
       int rc;
       const int64_t nl = (int64_t)lrow.size(), nc = (int64_t)ck.size() / 2;
-      if ((rc = upload(s, &s.d_long_row, lrow.data(), 4 * lrow.size()))) return rc;
-      if ((rc = upload(s, &s.d_long_cstart, lcs.data(), 4 * lcs.size()))) return rc;
-      if ((rc = upload(s, &s.d_chunk_k, ck.data(), 4 * ck.size()))) return rc;
-      if ((rc = dev_alloc(&s.d_partials, dtype_size(dtype) * (size_t)nc, &s.bytes))) return rc;
+      if ((rc = s.dev.upload(&s.d_long_row, lrow.data(), 4 * lrow.size()))) return rc;
+      if ((rc = s.dev.upload(&s.d_long_cstart, lcs.data(), 4 * lcs.size()))) return rc;
+      if ((rc = s.dev.upload(&s.d_chunk_k, ck.data(), 4 * ck.size()))) return rc;
+      if ((rc = s.dev.alloc(&s.d_partials, dtype_size(dtype) * (size_t)nc))) return rc;
       s.dp.long_t = kLongRow;
       s.dp.n_long = (int32_t)nl;
       s.dp.n_chunks = (int32_t)nc;
@@ -794,8 +791,8 @@ int build_plan_tables(Shard &s, unsigned flags) {
     if (fits && s.d_sl_desc) {
       // row slices: the launch reads the slice-major streams, one length per
       // row and one descriptor per task instead of the CSR-order streams and
-      // the row pointers; the CSR-order values of an owned matrix are freed
-      // (nothing this handle launches reads them)
+      // the row pointers; the CSR-order values of an owned matrix are released
+      // (nothing this handle launches reads them; a borrowed one has no d_val)
       s.dp.xd_blk = s.d_xd_blk;
       s.dp.xd_runs = s.d_xd_runs;
       s.dp.xd_lds_bytes = s.xd_lds_bytes;
@@ -807,11 +804,10 @@ int build_plan_tables(Shard &s, unsigned flags) {
       s.dp.sl_val = s.d_sl_val;
       s.dp.n_slices = (int32_t)s.sl_desc_n;
       s.plan.row_slices = true;
-      if (s.owns_csr && s.d_val) {
-        (void)hipFree(s.d_val);
+      if (s.d_val) {
+        s.dev.release(s.d_val);
         s.d_val = nullptr;
         s.A.val = nullptr;
-        s.bytes -= (int64_t)(sval * (double)s.A.nnz);
       }
       s.c16_saved = (double)s.A.nnz * (sval + 4.0) + 4.0 * (double)(m + 1) -
                     (64.0 * (double)s.sl_padded * sval + (double)s.sl_pos_bytes + (double)m +
@@ -854,14 +850,14 @@ int build_plan_tables(Shard &s, unsigned flags) {
   const std::vector<int32_t> &xw = s.plan.kernel == kStream ? s.h_xwin : s.h_xwin_t;
   if ((s.plan.kernel == kStream || (s.plan.kernel == kCsr3 && !s.h_tasks.empty())) && !xw.empty()) {
     int rc;
-    if ((rc = upload(s, &s.d_xwin, xw.data(), 4 * xw.size()))) return rc;
+    if ((rc = s.dev.upload(&s.d_xwin, xw.data(), 4 * xw.size()))) return rc;
     s.dp.xwin = s.d_xwin;
   }
   std::vector<int32_t>().swap(s.h_xwin);
   std::vector<int32_t>().swap(s.h_xwin_t);
   if (s.plan.kernel == kCsr3 && !s.h_tasks.empty()) {
     int rc;
-    if ((rc = upload(s, &s.d_task, s.h_tasks.data(), 4 * s.h_tasks.size()))) return rc;
+    if ((rc = s.dev.upload(&s.d_task, s.h_tasks.data(), 4 * s.h_tasks.size()))) return rc;
     s.dp.task_start = s.d_task;
     s.dp.n_tasks = (int32_t)(s.h_tasks.size() - 1);
     s.dp.task_align = ssr_aligned(s.tune) ? 1 : 0;

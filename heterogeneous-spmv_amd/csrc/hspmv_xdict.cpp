@@ -276,11 +276,11 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
     build_slices(rp, P.pos.data(), val, m, s.val_dtype, slice_starts(kern, m, s.h_tasks), S);
     if ((rc = upload_slices(s, S))) return rc;
     s.A.has_slices = true;
-  } else if ((rc = upload(s, &s.d_c16, P.pos.data(), 2 * P.pos.size()))) {
+  } else if ((rc = s.dev.upload(&s.d_c16, P.pos.data(), 2 * P.pos.size()))) {
     return rc;
   }
-  if ((rc = upload(s, &s.d_xd_blk, P.blk.data(), 4 * P.blk.size()))) return rc;
-  if ((rc = upload(s, &s.d_xd_runs, P.rec.data(), 4 * P.rec.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_xd_blk, P.blk.data(), 4 * P.blk.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_xd_runs, P.rec.data(), 4 * P.rec.size()))) return rc;
   s.A.col16 = slices ? s.d_sl_pos : s.d_c16;  // the 16-bit position stream the launch reads
   s.A.cbase = nullptr;
   s.A.cplanes = nullptr;
