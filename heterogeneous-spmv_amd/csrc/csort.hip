@@ -38,7 +38,9 @@
 // hspmv_csort_finish.
 #include <hip/hip_runtime.h>
 
+#include "dev_prims.cuh"
 #include "hspmv_internal.h"
+#include "static_switch.h"
 
 // Ablation builds only (wrong results by design; the csort-abl libraries of
 // the Makefile): 1 = the slot adds as ds_add_u64 of the bit pattern, 2 = no
@@ -52,37 +54,18 @@
 namespace hspmv {
 namespace {
 
-constexpr int kWave = 64;
+using dev::dpp_move;
+using dev::kWave;
+using dev::ldg;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-template <bool NT, typename P>
-__device__ __forceinline__ P ld(const P *p) {
-  if constexpr (NT)
-    return __builtin_nontemporal_load(p);
-  else
-    return *p;
-}
 
 __device__ __forceinline__ int32_t wave_uniform(int32_t v) {
   return __builtin_amdgcn_readfirstlane(v);
 }
 
-// One DPP move (both dwords for fp64); lanes the pattern does not feed read
-// `old` (keys: a sentinel no slot equals; values: 0).
-template <int CTRL, int ROW_MASK, typename S>
-__device__ __forceinline__ S dpp_val(S v) {
-  if constexpr (sizeof(S) == 8) {
-    const uint64_t b = __builtin_bit_cast(uint64_t, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), CTRL, ROW_MASK, 0xf, false);
-    return __builtin_bit_cast(S, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-  } else {
-    return __builtin_bit_cast(S, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL,
-                                                             ROW_MASK, 0xf, false));
-  }
-}
-
+// dpp_move for the scan's keys: lanes the pattern does not feed read a
+// sentinel no slot equals (the values: 0).
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint32_t dpp_key(uint32_t k) {
   return (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k, CTRL, ROW_MASK, 0xf, false);
@@ -97,7 +80,7 @@ __device__ __forceinline__ S seg_scan(S v, uint32_t k) {
 #define HSPMV_SEG_STEP(CTRL, MASK)                        \
   {                                                      \
     const uint32_t kp = dpp_key<CTRL, MASK>(k);          \
-    const S vp = dpp_val<CTRL, MASK>(v);                 \
+    const S vp = dpp_move<CTRL, MASK>(v);                 \
     v += kp == k ? vp : S(0);                            \
   }
   HSPMV_SEG_STEP(0x111, 0xf)
@@ -124,7 +107,7 @@ __device__ __forceinline__ void load_entries(const void *__restrict__ ent, const
       const u32x4 *p = reinterpret_cast<const u32x4 *>(reinterpret_cast<const u32x2 *>(ent) + k0) + lane;
 #pragma unroll
       for (int u = 0; u < U; u += 2) {
-        const u32x4 r = ld<NT>(p + (u / 2) * kWave);
+        const u32x4 r = ldg<NT>(p + (u / 2) * kWave);
         ix[u] = r.x;
         vv[u] = __uint_as_float(r.y);
         ix[u + 1] = r.z;
@@ -135,7 +118,7 @@ __device__ __forceinline__ void load_entries(const void *__restrict__ ent, const
       const u32x4 *pi = reinterpret_cast<const u32x4 *>(reinterpret_cast<const uint32_t *>(ent) + k0) + lane;
 #pragma unroll
       for (int u = 0; u < U; u += 4) {
-        const u32x4 r = ld<NT>(pi + (u / 4) * kWave);
+        const u32x4 r = ldg<NT>(pi + (u / 4) * kWave);
         ix[u] = r.x;
         ix[u + 1] = r.y;
         ix[u + 2] = r.z;
@@ -145,7 +128,7 @@ __device__ __forceinline__ void load_entries(const void *__restrict__ ent, const
       const f64x2 *pv = reinterpret_cast<const f64x2 *>(reinterpret_cast<const double *>(val) + k0) + lane;
 #pragma unroll
       for (int u = 0; u < U; u += 2) {
-        const f64x2 r = ld<NT>(pv + (u / 2) * kWave);
+        const f64x2 r = ldg<NT>(pv + (u / 2) * kWave);
         vv[u] = r.x;
         vv[u + 1] = r.y;
       }
@@ -156,12 +139,12 @@ __device__ __forceinline__ void load_entries(const void *__restrict__ ent, const
   for (int u = 0; u < U; ++u) {
     const int64_t k = k0 + lane + u * kWave;
     if constexpr (sizeof(T) == 4) {
-      const u32x2 p = ld<NT>(reinterpret_cast<const u32x2 *>(ent) + k);
+      const u32x2 p = ldg<NT>(reinterpret_cast<const u32x2 *>(ent) + k);
       ix[u] = p.x;
       vv[u] = __uint_as_float(p.y);
     } else {
-      ix[u] = ld<NT>(reinterpret_cast<const uint32_t *>(ent) + k);
-      vv[u] = ld<NT>(val + k);
+      ix[u] = ldg<NT>(reinterpret_cast<const uint32_t *>(ent) + k);
+      vv[u] = ldg<NT>(val + k);
     }
   }
 }
@@ -564,19 +547,15 @@ template <typename T, typename S, typename P, int U, bool NT>
 hipError_t launch_csort_p(const DevCsort &c, const T *x, T *y, hipStream_t st) {
   P *part = static_cast<P *>(c.part);
   S *spart = static_cast<S *>(c.spart);
-  if constexpr (sizeof(T) == 8 && U % 4 != 0) {
+  // fp64 wide entries come four to a load: no WIDE variant for other U
+  constexpr bool kWideOffered = !(sizeof(T) == 8 && U % 4 != 0);
+  if constexpr (!kWideOffered)
     if (c.wide) return hipErrorInvalidValue;
-    if (c.prefetch) launch_csort_main<T, S, P, U, NT, true, false>(c, x, part, spart, y, st);
-    else launch_csort_main<T, S, P, U, NT, false, false>(c, x, part, spart, y, st);
-  } else {
-    if (c.prefetch) {
-      if (c.wide) launch_csort_main<T, S, P, U, NT, true, true>(c, x, part, spart, y, st);
-      else launch_csort_main<T, S, P, U, NT, true, false>(c, x, part, spart, y, st);
-    } else {
-      if (c.wide) launch_csort_main<T, S, P, U, NT, false, true>(c, x, part, spart, y, st);
-      else launch_csort_main<T, S, P, U, NT, false, false>(c, x, part, spart, y, st);
-    }
-  }
+  static_flag(c.prefetch, [&](auto PF) {
+    static_flag<kWideOffered>(c.wide, [&](auto WIDE) {
+      launch_csort_main<T, S, P, U, NT, PF, WIDE>(c, x, part, spart, y, st);
+    });
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || c.direct) return e;
   // rows per finishing thread: 4 (32-byte partial loads; C5 104.4 -> 103.5
@@ -607,14 +586,13 @@ hipError_t launch_csort_u(const DevCsort &c, const T *x, T *y, hipStream_t st) {
   return launch_csort_p<T, S, S, U, NT>(c, x, y, st);
 }
 
-template <typename T, typename S, bool NT>
-hipError_t launch_csort_nt(const DevCsort &c, const T *x, T *y, hipStream_t st) {
-  switch (c.u) {
-    case 4: return launch_csort_u<T, S, 4, NT>(c, x, y, st);
-    case 8: return launch_csort_u<T, S, 8, NT>(c, x, y, st);
-    case 16: return launch_csort_u<T, S, 16, NT>(c, x, y, st);
-    default: return hipErrorInvalidValue;
-  }
+template <typename T, typename S>
+hipError_t launch_csort_s(const DevCsort &c, const T *x, T *y, hipStream_t st) {
+  hipError_t e = hipErrorInvalidValue;  // entries per lane and chunk: 4, 8 or 16
+  static_flag(c.nontemporal, [&](auto NT) {
+    static_switch<4, 8, 16>(c.u, [&](auto U) { e = launch_csort_u<T, S, U, NT>(c, x, y, st); });
+  });
+  return e;
 }
 
 }  // namespace
@@ -626,16 +604,10 @@ hipError_t launch_csort(const DevCsort &c, int dtype, const void *x, void *y, hi
     return hipErrorInvalidValue;
   if (dtype == 1) {
     if (c.slot32) return hipErrorInvalidValue;
-    return c.nontemporal ? launch_csort_nt<double, double, true>(c, (const double *)x, (double *)y, st)
-                         : launch_csort_nt<double, double, false>(c, (const double *)x, (double *)y, st);
+    return launch_csort_s<double, double>(c, (const double *)x, (double *)y, st);
   }
-  const float *xf = (const float *)x;
-  float *yf = (float *)y;
-  if (c.slot32)
-    return c.nontemporal ? launch_csort_nt<float, float, true>(c, xf, yf, st)
-                         : launch_csort_nt<float, float, false>(c, xf, yf, st);
-  return c.nontemporal ? launch_csort_nt<float, double, true>(c, xf, yf, st)
-                       : launch_csort_nt<float, double, false>(c, xf, yf, st);
+  if (c.slot32) return launch_csort_s<float, float>(c, (const float *)x, (float *)y, st);
+  return launch_csort_s<float, double>(c, (const float *)x, (float *)y, st);
 }
 
 }  // namespace hspmv

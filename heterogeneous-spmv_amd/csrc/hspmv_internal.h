@@ -287,7 +287,7 @@ struct DevPlan {
   int32_t xd_lds_bytes = 0;
   // Row slices (hspmv_slices.cpp): the dictionary handle's matrix stored per
   // 64-row wave task column-major, one lane per row (hspmv_slices,
-  // spmv_device.cuh).  sl_desc: {prefix, first row} per task and a closing
+  // slice_kernel.cuh).  sl_desc: {prefix, first row} per task and a closing
   // pair ({padded slot columns, m}); slice t's values start at sl_val + 64 *
   // prefix elements; sl_len: one length per row.  Positions: sl_pos_bits =
   // 16, slice t's start at sl_pos + 64 * prefix; 12, the packed stream, slice
@@ -326,7 +326,7 @@ struct LaunchPlan {
   bool reverse = false;    // STREAM/CSR3/slices: this launch sweeps the blocks last to first (launch_spmv)
   int32_t groups = 1;      // STREAM: 64-row groups per wave (next group's rp prefetched)
   int32_t carry = 0;       // STREAM/CSR3: rows start from y (x-slab passes after the first)
-  bool lds_pad = false;     // STREAM: bank-padded product buffers (spmv_device.cuh lds_ix)
+  bool lds_pad = false;     // STREAM: bank-padded product buffers (row_kernels.cuh lds_ix)
   bool row_slices = false;  // STREAM/CSR3 with dictionaries: the lane-per-row slice kernel
   int64_t blocks = 0;
 };

@@ -58,7 +58,7 @@ LaunchPlan plan_launch(const DevCSR &A, int dtype, int val_dtype, unsigned flags
   // from HBM the dispatch order (the whole chip on one compact window)
   // streams 3-8 % faster (profiles/r01_sweep2-4: C2 full remap 15.6 vs
   // 16.9 us; C3 132 vs 128, C4 70.6 vs 65.4).  Chunked orders in between:
-  // xcd_chunk_remap in spmv_device.cuh.
+  // xcd_chunk_remap in hspmv_internal.h.
   // sv: bytes of an x entry; sval: of a stored value (a mixed handle: 8 and 4)
   const double sv = dtype == HSPMV_F64 ? 8.0 : 4.0;
   const double sval = val_dtype == HSPMV_F64 ? 8.0 : 4.0;
@@ -137,7 +137,7 @@ LaunchPlan plan_launch(const DevCSR &A, int dtype, int val_dtype, unsigned flags
     }
   }
   // The STREAM / CSR3 kernels address x and the matrix streams as a 64-bit
-  // base plus a 32-bit byte offset (spmv_device.cuh ld_off): x of 4 GiB or
+  // base plus a 32-bit byte offset (dev_prims.cuh ld_off): x of 4 GiB or
   // more (fp64: n >= 2^29), or -- without split rows -- a row group that
   // could stream 4 GiB, would wrap.  Such matrices take a kernel that
   // indexes through pointers: csort when it was built, else VECTOR.

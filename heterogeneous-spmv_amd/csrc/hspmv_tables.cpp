@@ -629,7 +629,7 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
                      int64_t n, unsigned flags) {
   const int dtype = s.dtype;  // the vectors'; the values': s.val_dtype
   // the typical serially summed row (median length of the rows of 1..40
-  // nonzeros, spmv_device.cuh kSerialMax): the planner's LDS bank rule
+  // nonzeros, kSerialMax): the planner's LDS bank rule
   {
     constexpr int kSerial = kSerialMax;
     int64_t hist[kSerial + 1] = {0}, tot = 0;

@@ -179,7 +179,7 @@ int64_t xd_target_entries(int dtype, const Tuning &t, bool slices) {
   const int64_t sv = (int64_t)dtype_size(dtype);
   // product staging of the chunk plan_launch picks for >= 12 nonzeros per
   // row (pick_u: U = 4 fp64, 16 fp32), 4 waves (CSR3 product buffers are
-  // never bank-padded: spmv_device.cuh wave_lds<U, false>)
+  // never bank-padded: row_kernels.cuh wave_lds<U, false>)
   const int64_t staging = slices ? 0 : 4 * 64 * (sv == 8 ? 4 : 16) * sv + 16;
   const int64_t per_block = (kLdsPerCu / bpc) / kLdsGranule * kLdsGranule;
   return std::max<int64_t>(0, (per_block - staging) / sv);

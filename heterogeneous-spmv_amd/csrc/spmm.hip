@@ -34,9 +34,10 @@
 // All index arithmetic into X and Y is 64-bit (n * ldx may exceed 2^31).
 // LDS is static only.  Out of scope here: multi-GPU shards, k > 32, CSR-3
 // maps, x dictionaries or row slices for X, column-major X, alpha / beta.
-#include "spmv_device.cuh"
-
+#include "dev_prims.cuh"
 #include "hspmv_common.h"
+#include "hspmv_internal.h"
+#include "static_switch.h"
 
 namespace hspmv {
 namespace {
@@ -173,15 +174,10 @@ hipError_t launch_kp(const DevMM &d, int64_t blocks, const T *X, int64_t ldx, T 
 template <typename T, bool NT>
 hipError_t launch_typed(const DevMM &d, int64_t blocks, const T *X, int64_t ldx, T *Y, int64_t ldy,
                         hipStream_t st) {
-  switch (d.lanes_per_row) {
-    case 1: return launch_kp<T, 1, NT>(d, blocks, X, ldx, Y, ldy, st);
-    case 2: return launch_kp<T, 2, NT>(d, blocks, X, ldx, Y, ldy, st);
-    case 4: return launch_kp<T, 4, NT>(d, blocks, X, ldx, Y, ldy, st);
-    case 8: return launch_kp<T, 8, NT>(d, blocks, X, ldx, Y, ldy, st);
-    case 16: return launch_kp<T, 16, NT>(d, blocks, X, ldx, Y, ldy, st);
-    case 32: return launch_kp<T, 32, NT>(d, blocks, X, ldx, Y, ldy, st);
-    default: return hipErrorInvalidValue;
-  }
+  hipError_t e = hipErrorInvalidValue;  // lanes per row: a power of two up to 32
+  static_switch<1, 2, 4, 8, 16, 32>(d.lanes_per_row,
+                                    [&](auto KP) { e = launch_kp<T, KP, NT>(d, blocks, X, ldx, Y, ldy, st); });
+  return e;
 }
 
 }  // namespace

@@ -1,52 +1,6 @@
-// spmv_kernels.hip -- hand-written CDNA4 (gfx950) SpMV kernels.
-//
-// The hot path of the reference is the row-wise nonzero dot product
-//   y[r] = sum_{k=rp[r]}^{rp[r+1]-1} val[k] * x[col[k]]
-// (spmv-csr/spmv.c:92-114; GPU forms cuda-spmv-csr/spmv.cu:117-182 and
-// cuda-spmv-csrk/hip/csrk.cu:185-390).  It is an HBM-bound gather: 2 flops per
-// 12 B (fp64) / 8 B (fp32) of matrix stream, so no MFMA anywhere here.
-//
-// Kernels (all wave64-native):
-//
-//  * hspmv_csr_stream<T, NT, U>   (HSPMV_KERNEL_STREAM, the default for CSR)
-//      one wavefront per group of 64 consecutive rows.  The group's nonzeros
-//      are contiguous, so the wave streams them with fully coalesced loads
-//      (U elements per lane per chunk), forms the products val*x[col] and
-//      stages them in a per-wave LDS slice.  Then
-//        - rows of <= kSerialMax nonzeros: lane i sums row i left to right.
-//          Summation order and rounding (product rounded, then sum rounded,
-//          starting from 0) are those of omp_spmv, so these rows are
-//          BIT-IDENTICAL to the CPU reference;
-//        - longer rows: the whole wave sums the row's products in the chunk
-//          (shuffle tree), accumulated over chunks (fp64 tolerance);
-//        - split rows (> kLongRow nonzeros) are skipped here and summed by
-//          hspmv_long_chunks + hspmv_long_reduce (many workgroups per row).
-//      The serial bound is an argument (DevPlan.serial_max): with
-//      hspmv_options.deterministic = 3 every row takes the first branch,
-//      and split rows go to hspmv_long_serial (one workgroup per row, the
-//      adds still in order, on a stream forked beside this kernel) +
-//      hspmv_long_scatter.
-//      Replaces cuda_spmv's thread-per-row scalar loop (uncoalesced) with a
-//      CSR-stream scheme (coalesced stream + LDS segmented sums).
-//
-//  * hspmv_csr3<T, NT, U, W>      (HSPMV_KERNEL_CSR3)
-//      CSR-3: wave tasks planned on the host, four per workgroup: 64-row
-//      aligned groups by default (cache-line-aligned y stores), super-rows
-//      packed into <= 64-row tasks (HSPMV_TASK_FILL=0), or one workgroup of
-//      W waves per super-super-row whose super-rows are split W ways by
-//      nonzeros (HSPMV_CSR3_PLAN=ssr); each wave runs the stream routine
-//      over its task (hspmv_tables.cpp build_tasks).  Replaces cuSpMV_3 / cuSpMV_3_vec (thread or
-//      sub-warp per row inside (8,12)-thread blocks, csrk.cu:185-319) and
-//      cuSpMV_2 (degenerate outer level).
-//
-//  * hspmv_slices<T, NT, B, PB>   (STREAM / CSR3 handles with row slices)
-//      the transposed shape of the two kernels above for dictionary handles
-//      whose rows are all summed serially: the wave's 64-row task is stored
-//      slot-major (hspmv_slices.cpp), lane i multiplies and adds row i left
-//      to right out of 16-byte value and 8-byte position loads (PB = 12,
-//      dictionaries of <= 4096 entries: one 12-byte load of eight 12-bit
-//      positions), B slots per batch, the next batch in flight.  Same bits,
-//      no product buffer, no row pointers (spmv_device.cuh "row slices").
+// spmv_kernels.hip -- launch_spmv, the entry of every single-vector SpMV, and
+// the kernels that are not row kernels (those: row_kernels.cuh and
+// slice_kernel.cuh, instantiated by the stream_* units; csort.hip):
 //
 //  * hspmv_csr_vector<T, L, NT>   (HSPMV_KERNEL_VECTOR)
 //      L lanes (a sub-wave, L | 64) per row, lanes stride the row's nonzeros
@@ -55,12 +9,11 @@
 //      (csrk.cu:222-240) with a wave64-safe shuffle reduction; L = 1 is the
 //      thread-per-row cuda_spmv shape.
 //
-// Blocks are remapped so each of the 8 XCDs (private 4 MiB L2 each) gets a
-// contiguous range of row groups: neighbouring rows share x[] lines and the
-// edges of val/col lines, which then hit in one L2 instead of eight.  Every
-// other SpMV of a handle whose matrix exceeds the Infinity Cache runs that
-// order mirrored, last block first (sweep_block, hspmv_internal.h;
-// hspmv_set_sweep), and so begins on the bytes the cache still holds.
+//  * the split rows (> kLongRow nonzeros) that the row kernels skip:
+//    hspmv_long_chunks + hspmv_long_reduce (many workgroups per row), or with
+//    hspmv_options.deterministic = 3 hspmv_long_serial (one workgroup per
+//    row, the adds still in order, on a stream forked beside the row kernel)
+//    + hspmv_long_scatter.
 //
 // Build: hipcc --offload-arch=gfx950 -ffp-contract=off.  Contraction is off so
 // that only the explicit fma() calls (vector kernel, long rows) fuse.
@@ -68,27 +21,16 @@
 
 #include <cstdlib>
 
+#include "dev_prims.cuh"
 #include "hspmv_internal.h"
+#include "static_switch.h"
 
 namespace hspmv {
 namespace {
 
-constexpr int kWave = 64;
-
-template <bool NT, typename T>
-__device__ __forceinline__ T ldg(const T *p) {
-  if constexpr (NT)
-    return __builtin_nontemporal_load(p);
-  else
-    return *p;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
+using dev::kWave;
+using dev::ldg;
+using dev::wave_sum;
 
 // TV (here and in the split-row kernels): the stored type of val -- T, or
 // float under T = double for the mixed handles; a value is widened to T before
@@ -281,18 +223,11 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
   }
   switch (p.kernel) {
     case kVector:
-      switch (p.lanes) {
-#define HSPMV_VEC(L)                                                                    \
-  case L:                                                                               \
-    hipLaunchKernelGGL((hspmv_csr_vector<T, L, NT, TV>), dim3((unsigned)p.blocks), dim3(256), \
-                       0, st, A.m, rp, ci, val, x, y);                                  \
-    break;
-        HSPMV_VEC(1) HSPMV_VEC(2) HSPMV_VEC(4) HSPMV_VEC(8) HSPMV_VEC(16)
-        HSPMV_VEC(32) HSPMV_VEC(64)
-#undef HSPMV_VEC
-        default:
-          return hipErrorInvalidValue;
-      }
+      if (!static_switch<1, 2, 4, 8, 16, 32, 64>(p.lanes, [&](auto L) {
+            hipLaunchKernelGGL((hspmv_csr_vector<T, L, NT, TV>), dim3((unsigned)p.blocks), dim3(256), 0, st, A.m,
+                               rp, ci, val, x, y);
+          }))
+        return hipErrorInvalidValue;
       return hipGetLastError();  // the vector kernel sums split rows itself
     case kStream:
     case kCsr3:

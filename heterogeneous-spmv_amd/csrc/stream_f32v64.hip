@@ -2,7 +2,7 @@
 // the mixed handles: values stored and streamed as float, x, y, the products
 // and the sums double (hspmv_create_mixed).  A unit of its own, like
 // stream_f32.hip / stream_f64.hip, so hipcc compiles the three in parallel.
-#include "spmv_device.cuh"
+#include "row_launch.cuh"
 
 namespace hspmv {
 hipError_t launch_rows_f32v64(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const double *x,

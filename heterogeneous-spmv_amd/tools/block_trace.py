@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-workgroup timeline of the CSR3 kernel from the diag-512 build (make
-diag DIAGS=512; HSPMV_DIAG & 512 in csrc/spmv_device.cuh): start and each
+diag DIAGS=512; HSPMV_DIAG & 512, kDiagBlockTrace in csrc/dev_diag.cuh): start and each
 wave's end per workgroup (s_memrealtime, 100 MHz), XCD.  Shows the launch's
 ramp-up and tail: how many workgroups are live over time, and how long a
 workgroup lives.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-wave phase timing of the STREAM fp64 kernel from the diag-8 build
-(make diag; HSPMV_DIAG & 8 in csrc/spmv_device.cuh).  Each wave's lane 0
+(make diag; HSPMV_DIAG & 8, kDiagWaveTrace in csrc/dev_diag.cuh).  Each wave's lane 0
 stamps s_memtime at: start, row bounds loaded, first chunk's col/val
 arrived, its x gather arrived, its row sums done, and the end; every stamp
 waits for the wave's outstanding loads, so the phases are serialised.

@@ -1,6 +1,6 @@
 """The XCD block order is a bijection on [0, nb) for every chunk size.
 
-Restates xcd_chunk_remap (heterogeneous-spmv_amd/csrc/spmv_device.cuh) in
+Restates xcd_chunk_remap (heterogeneous-spmv_amd/csrc/hspmv_internal.h) in
 numpy; a non-bijective order would leave rows of y unwritten, which a parity
 test can miss when y's buffer still holds an earlier, equal result.
 """

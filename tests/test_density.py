@@ -155,3 +155,34 @@ def test_bank_padded_product_buffers_on_32_nonzero_rows(dtype):
     short = np.diff(S.row_ptr) <= 40
     rs = oracle.spmv(S.row_ptr, S.col_idx, S.val, xs)
     assert np.array_equal(ys[short].view(np.uint8), rs[short].view(np.uint8))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_bank_padded_stream_in_every_workgroup_shape(dtype):
+    """The padded STREAM kernels exist for 1, 2 and 4 waves per workgroup, each
+    with and without x windows (row_launch.cuh): dense 32 x 32 diagonal blocks
+    over 4 * 64 * 3 + 37 rows -- several workgroups at every shape, a partial
+    last 64-row group -- must plan the padded buffers in all six shapes, run
+    the shape asked for, and give the reference's left-to-right sums bit for
+    bit."""
+    m, b = 4 * 64 * 3 + 37, 32
+    n = (m + b - 1) // b * b  # the last block's rows keep 32 nonzeros
+    rows = np.arange(m, dtype=np.int64)
+    ci = ((rows // b) * b)[:, None] + np.arange(b, dtype=np.int64)[None, :]
+    rng = np.random.default_rng(11)
+    rp = np.arange(0, m * b + 1, b, dtype=np.int64).astype(np.int32)
+    A = hspmv.CsrMatrix(m, n, rp, ci.reshape(-1).astype(np.int32), rng.uniform(-1, 1, m * b).astype(dtype))
+    x = gen.rand_x(A.n, 6).astype(dtype)
+    ref = oracle.spmv(A.row_ptr, A.col_idx, A.val, x)
+    for waves in (1, 2, 4):
+        for xwin in (1, 0):
+            opts = {"x_dict": -1, "stream_waves": waves}
+            if not xwin:
+                opts["x_windows"] = -1
+            y, info = run(A, x, kernel="stream", options=opts)
+            shape = (waves, xwin)
+            assert info["lds_pad"] == 1, shape
+            assert info["waves_per_block"] == waves, shape
+            assert info["x_windows"] == xwin, shape
+            assert np.array_equal(y.view(np.uint8), ref.view(np.uint8)), shape

@@ -1,5 +1,5 @@
 """Row slices: the lane-per-row kernel of dictionary handles whose rows are
-all summed serially (hspmv_slices.cpp, spmv_device.cuh hspmv_slices).
+all summed serially (hspmv_slices.cpp, slice_kernel.cuh hspmv_slices).
 
 Host: hspmv_slices_plan's arrays hold exactly the input CSR (values, and the
 columns through the dictionary run records), its counts match the CPU model

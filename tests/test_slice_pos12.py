@@ -1,5 +1,5 @@
 """Row slices with 12-bit dictionary positions (hspmv_slices_pack,
-spmv_device.cuh hspmv_slices<.., PB = 12>).
+slice_kernel.cuh hspmv_slices<.., PB = 12>).
 
 Host: the packed stream unpacks, in numpy, to hspmv_slices_plan's 16-bit
 positions for every slice width; the bit width follows the largest

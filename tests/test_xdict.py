@@ -2,7 +2,7 @@
 
 The STREAM / CSR3 kernels can stage, per workgroup, the x entries its rows
 reference (runs of consecutive columns) in LDS and gather through 16-bit
-positions (spmv_device.cuh stage_xdict).  These tests check the format the
+positions (row_kernels.cuh stage_xdict).  These tests check the format the
 host builds: every in-kernel nonzero's position addresses exactly x[col],
 runs are sorted, disjoint and at most 63 per workgroup, the per-block
 entries respect the cap, and split rows are left out.  The GPU side is
