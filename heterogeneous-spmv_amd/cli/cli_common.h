@@ -45,6 +45,15 @@
 //                       column ones); flops = 2 nnz K; prints "Rhs: K"; the
 //                       check runs per column; --dump-y writes the row-major
 //                       m x K array.  One GPU, the automatic kernel only.
+//   --update-values N   after the timed loop and its report: N rounds of
+//                       hspmv_update_values on the planned handle from host
+//                       memory, round k with the file's values times 1 +
+//                       2^-(k+1); prints "UpdateMin:" / "UpdateAvg:" (wall
+//                       seconds per call), then runs one SpMV and prints
+//                       "UpdateCheck: PASS|FAIL ..." against the serial CPU
+//                       sum over the last round's values (not with --rhs;
+//                       a band-k order keeps its permutation: the values are
+//                       those of the matrix the handle was created from)
 //   --dump-y PATH       write y as raw binary (dtype) for external checks
 //   --no-check          skip the serial CPU check
 #pragma once
@@ -75,6 +84,7 @@ struct Options {
   int sweep = HSPMV_SWEEP_AUTO;  // hspmv_set_sweep
   bool check = true;
   int rhs = 0;  // > 0: the multi-vector operator with this many right-hand sides
+  int update_values = 0;  // > 0: rounds of hspmv_update_values after the timed loop
   std::string dump_y;
   std::string params = "mi355x";
   bool bandk = true;  // spmv-csrk on a .csr: band-k reorder (the reference's CSRk_Graph)
@@ -147,6 +157,10 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
       const char *v = need("--rhs"); if (!v) return false;
       o.rhs = atoi(v);
       if (o.rhs < 1 || o.rhs > 32) { fprintf(stderr, "bad --rhs %s (1..32)\n", v); return false; }
+    } else if (a == "--update-values") {
+      const char *v = need("--update-values"); if (!v) return false;
+      o.update_values = atoi(v);
+      if (o.update_values < 1) { fprintf(stderr, "bad --update-values %s (>= 1)\n", v); return false; }
     } else if (a == "--no-check") {
       o.check = false;
     } else if (a == "--dump-y") {
@@ -169,6 +183,7 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
       fprintf(stderr, "--rhs takes no --plan, --deterministic, --reproducible, --serial or --sweep\n");
       return false;
     }
+    if (o.update_values > 0) { fprintf(stderr, "--rhs takes no --update-values\n"); return false; }
   }
   return true;
 }
@@ -426,6 +441,46 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
     if (o.deterministic == HSPMV_DETERMINISTIC_SERIAL) {  // the serial order's contract
       printf("Bitwise: %lld rows differ\n", (long long)r.bit_diff);
       if (r.bit_diff) rc = 2;
+    }
+  }
+  if (o.update_values > 0) {
+    // new values on the planned handle, N rounds: round k holds the file's
+    // values times 1 + 2^-(k+1); then one SpMV, checked against the serial
+    // sum over the last round's values
+    const size_t svv = A.dtype == HSPMV_F64 ? 8 : 4;
+    std::vector<char> nv(svv * (size_t)(A.nnz ? A.nnz : 1));
+    double umin = 1e30, usum = 0.0;
+    for (int k = 0; k < o.update_values; ++k) {
+      const double f = 1.0 + ldexp(1.0, -(k + 1));
+      for (int64_t i = 0; i < A.nnz; ++i) {
+        if (A.dtype == HSPMV_F64)
+          ((double *)nv.data())[i] = ((const double *)A.val)[i] * f;
+        else
+          ((float *)nv.data())[i] = (float)((double)((const float *)A.val)[i] * f);
+      }
+      const auto tic = std::chrono::steady_clock::now();
+      if (hspmv_update_values(h, nv.data(), 0) != HSPMV_OK) return die("hspmv_update_values");
+      const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
+      umin = dt < umin ? dt : umin;
+      usum += dt;
+    }
+    printf("UpdateMin: %lg\n", umin);
+    printf("UpdateAvg: %lg\n", usum / o.update_values);
+    if (hspmv_spmv(h) != HSPMV_OK) return die("hspmv_spmv");
+    if (hspmv_get_y(h, y.data()) != HSPMV_OK) return die("hspmv_get_y");
+    if (o.check) {
+      CheckResult r;
+      if (vdt == HSPMV_F64 && A.dtype == HSPMV_F32) {
+        const float *v32 = (const float *)nv.data();
+        const std::vector<double> v64(v32, v32 + A.nnz);
+        r = check_y<double>(A, v64.data(), x64.data(), (const double *)y.data());
+      } else if (A.dtype == HSPMV_F64) {
+        r = check_y<double>(A, (const double *)nv.data(), x64.data(), (const double *)y.data());
+      } else {
+        r = check_y<float>(A, (const float *)nv.data(), x32.data(), (const float *)y.data());
+      }
+      printf("UpdateCheck: %s maxrel=%.3e wrong=%d\n", r.pass ? "PASS" : "FAIL", r.maxrel, r.wrong);
+      if (!r.pass) rc = 2;
     }
   }
   hspmv_destroy(h);

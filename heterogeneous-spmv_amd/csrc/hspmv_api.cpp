@@ -267,6 +267,35 @@ int hspmv_set_x(hspmv_handle *h, const void *x_host) {
   return HSPMV_OK;
 }
 
+int hspmv_update_values(hspmv_handle *h, const void *val, unsigned flags) {
+  clear_error();
+  int rc;
+  // every refusal, for every shard, before the first device call
+  if ((rc = check_handle(h))) return rc;
+  if (flags & ~HSPMV_VALUES_DEVICE)
+    return set_error(HSPMV_E_INVALID, "unknown flag bits 0x%x (HSPMV_VALUES_DEVICE or 0)",
+                     flags & ~HSPMV_VALUES_DEVICE);
+  const bool on_device = (flags & HSPMV_VALUES_DEVICE) != 0;
+  const bool borrowed = (h->flags & HSPMV_FLAG_DEVICE_PTRS) != 0;
+  if (borrowed && !on_device)
+    return set_error(HSPMV_E_INVALID, "a handle over borrowed device arrays (HSPMV_FLAG_DEVICE_PTRS) takes "
+                                      "device values only: pass HSPMV_VALUES_DEVICE");
+  if (on_device && h->shards.size() > 1)
+    return set_error(HSPMV_E_INVALID, "HSPMV_VALUES_DEVICE needs a single-device handle (this one has %d "
+                                      "shards): pass the global values from host memory",
+                     (int)h->shards.size());
+  for (const Shard &s : h->shards)
+    if ((rc = update_values_why(s))) return rc;
+  if (h->nnz == 0) return HSPMV_OK;
+  if (!val && !borrowed) return set_error(HSPMV_E_INVALID, "val is NULL");
+  const size_t sv = dtype_size(h->val_dtype);
+  for (Shard &s : h->shards) {
+    const void *v = val ? (const char *)val + sv * (size_t)s.nnz0 : nullptr;
+    if ((rc = update_shard_values(s, v, on_device, borrowed))) return rc;
+  }
+  return HSPMV_OK;
+}
+
 int hspmv_bind_x_device(hspmv_handle *h, const void *x_dev) {
   clear_error();
   int rc;

@@ -370,6 +370,19 @@ hipError_t launch_csort(const DevCsort &c, int dtype, const void *x, void *y, hi
 hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, int val_dtype, const LaunchPlan &plan,
                        const void *x, void *y, hipStream_t stream, bool reverse = false);
 
+// ---- value refresh (refresh.hip; hspmv_update_values, hspmv_update.cpp):
+// the derived copies of the values rebuilt on the device from src, the new
+// values in the shard's CSR order (val_dtype: the stored values').  Both
+// enqueue one kernel on st, or nothing for an empty table.
+// The row slices' value stream dst (DevPlan.sl_val) of n_slices descriptors
+// desc with the row lengths len; row_ptr: the shard's CSR row pointers.
+hipError_t launch_refresh_slices(int val_dtype, int64_t n_slices, const int32_t *desc, const uint8_t *len,
+                                 const int32_t *row_ptr, const void *src, void *dst, hipStream_t st);
+// The x slabs' slab-major values dst (DevPlan.slab_val) of the n_slabs
+// row-pointer arrays slab_rp, m + 1 entries each.
+hipError_t launch_refresh_slabs(int val_dtype, int32_t m, int64_t nnz, int32_t n_slabs, const int32_t *row_ptr,
+                                const int32_t *slab_rp, const void *src, void *dst, hipStream_t st);
+
 // ---- multi-vector SpMM (spmm.hip, hspmv_mm.cpp): Y = A X, X row-major n x k
 constexpr int32_t kMmMaxRhs = 32;
 // Lanes one row takes: the smallest power of two >= k (k in [1, kMmMaxRhs]).

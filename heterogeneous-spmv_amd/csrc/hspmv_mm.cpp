@@ -27,6 +27,7 @@ struct hspmv_mm {
   int32_t k = 1;
   int64_t ldx = 1, ldy = 1;  // leading dimensions of x / y
   bool x_set = false;
+  bool borrowed = false;                // HSPMV_FLAG_DEVICE_PTRS: d.val is the caller's
 };
 
 namespace hspmv {
@@ -59,6 +60,7 @@ int build_mm(hspmv_mm *mm, const hspmv_csr *A, bool borrowed, int device, void *
   DevMM &d = mm->d;
   const size_t sv = dtype_size(A->dtype);
   int rc;
+  mm->borrowed = borrowed;
   if ((rc = check_device(device))) return rc;
   dev.device = device;
   HIP_TRY(hipSetDevice(device));
@@ -152,6 +154,31 @@ int hspmv_mm_set_x(hspmv_mm *mm, const void *X_host, int64_t ldx) {
   mm->x = mm->d_x;
   mm->ldx = mm->k;
   mm->x_set = true;
+  return HSPMV_OK;
+}
+
+int hspmv_mm_update_values(hspmv_mm *mm, const void *val, unsigned flags) {
+  clear_error();
+  int rc;
+  if ((rc = check_mm(mm))) return rc;
+  if (flags & ~HSPMV_VALUES_DEVICE)
+    return set_error(HSPMV_E_INVALID, "unknown flag bits 0x%x (HSPMV_VALUES_DEVICE or 0)",
+                     flags & ~HSPMV_VALUES_DEVICE);
+  const bool on_device = (flags & HSPMV_VALUES_DEVICE) != 0;
+  if (mm->borrowed && !on_device)
+    return set_error(HSPMV_E_INVALID, "an operator over borrowed device arrays (HSPMV_FLAG_DEVICE_PTRS) "
+                                      "takes device values only: pass HSPMV_VALUES_DEVICE");
+  if (mm->nnz == 0) return HSPMV_OK;
+  if (mm->borrowed) {  // the kernels read the caller's array: nothing derived from it
+    if (val) mm->d.val = val;
+    return HSPMV_OK;
+  }
+  if (!val) return set_error(HSPMV_E_INVALID, "val is NULL");
+  hipStream_t st = mm->dev.stream;
+  HIP_TRY(hipSetDevice(mm->dev.device));
+  HIP_TRY(hipMemcpyAsync(const_cast<void *>(mm->d.val), val, dtype_size(mm->dtype) * (size_t)mm->nnz,
+                         on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  if (!on_device) HIP_TRY(hipStreamSynchronize(st));  // the host array is the caller's again
   return HSPMV_OK;
 }
 

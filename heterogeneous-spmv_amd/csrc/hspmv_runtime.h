@@ -13,6 +13,7 @@
 //                          plan entry points' shared preamble (plan_shape)
 //   hspmv_slices.cpp       row slices of dictionary handles (+ hspmv_slices_plan)
 //   hspmv_csort_build.cpp  column-sorted row blocks (csort.hip's tables)
+//   hspmv_update.cpp       new values for a planned shard (hspmv_update_values)
 //   hspmv_multi.cpp        the row-range partition over devices, RCCL
 //   hspmv_api.cpp          the C ABI entry points
 //
@@ -111,6 +112,7 @@ struct DevCtx {
 struct Shard {
   DevCtx dev;
   int64_t row0 = 0;  // first global row
+  int64_t nnz0 = 0;  // first global nonzero (hspmv_update_values: the shard's range of val)
   // dtype: x, y, the products and the sums; val_dtype: the stored values
   // (A.val, the slab and slice copies).  Equal, or HSPMV_F32 under HSPMV_F64
   // (hspmv_create_mixed).  Set before upload_shard / build_row_tables.
@@ -319,6 +321,18 @@ void drop_slices(Shard &s);
 // ---- hspmv_csort_build.cpp
 int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
                 int64_t n, int dtype, unsigned flags);
+
+// ---- hspmv_update.cpp
+// HSPMV_OK when the shard's plan can take new values, else HSPMV_E_INVALID
+// with the message set (the column-sorted kernel).  No device call.
+int update_values_why(const Shard &s);
+// New values for the shard: val = its nnz values in CSR order (host memory,
+// or on_device: on the shard's device); borrowed: the shard reads the
+// caller's device array -- val (NULL: the array as it is) is that array from
+// now on.  Copies into the CSR-order values the shard owns and rebuilds the
+// row slices' and the x slabs' copies on the shard's stream; a host val is
+// consumed before return.  The arguments were checked by the caller.
+int update_shard_values(Shard &s, const void *val, bool on_device, bool borrowed);
 
 // ---- hspmv_multi.cpp
 // (equal dtypes only: hspmv_create_mixed refuses more than one device)

@@ -169,6 +169,7 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
   const int64_t nnz = k1 - k0;
   HIP_TRY(hipSetDevice(s.dev.device));
   s.row0 = r0;
+  s.nnz0 = k0;
   int rc;
   std::vector<int32_t> &rp = s.h_rp;
   rp.resize((size_t)(m + 1));

@@ -1,0 +1,89 @@
+// hspmv_update.cpp -- new matrix values for a planned shard, in place
+// (hspmv_update_values; see hspmv_runtime.h for the split of the host runtime).
+#include <cstddef>
+
+#include "hspmv_runtime.h"
+
+namespace hspmv {
+
+// The plan of a shard depends on the sparsity pattern alone; the values sit in
+// up to three device arrays:
+//   CSR order   d_val (A.val): what the chunked STREAM / CSR3 kernels (32- or
+//               16-bit columns, dictionaries, x windows), VECTOR, the split-row
+//               and the serial long-row kernels read.  A row-slice shard has
+//               released it, a borrowed one never had it (A.val is the caller's);
+//   row slices  d_sl_val, slice-major (build_slices);
+//   x slabs     d_slab_val, slab-major (build_xslabs); split rows stay in A.val.
+// An update puts the new CSR-order values where A.val points -- a copy into
+// d_val, or the caller's array itself for a borrowed shard -- and rebuilds, on
+// the shard's stream, each derived copy the DevPlan launches from
+// (refresh.hip).  A row-slice shard that owns its matrix has no CSR-order
+// array to copy into: a device source is read where it is, a host source goes
+// through a staging allocation that lives for this call only.
+// Everything is enqueued on the shard's stream, after the SpMVs enqueued so
+// far and before the later ones; a host source is consumed (the stream
+// synchronised) before return.
+
+static int refresh_derived(Shard &s, const void *src) {
+  hipStream_t st = s.dev.stream;
+  if (s.dp.sl_desc) {
+    const hipError_t e = launch_refresh_slices(s.val_dtype, s.dp.n_slices, s.dp.sl_desc, s.dp.sl_len,
+                                               s.A.row_ptr, src, s.d_sl_val, st);
+    if (e != hipSuccess)
+      return set_error(HSPMV_E_HIP, "row-slice value refresh on GPU %d failed: %s", s.dev.device,
+                       hipGetErrorString(e));
+  }
+  if (s.dp.n_slabs) {
+    const hipError_t e = launch_refresh_slabs(s.val_dtype, s.A.m, s.A.nnz, s.dp.n_slabs, s.A.row_ptr,
+                                              s.dp.slab_rp, src, s.d_slab_val, st);
+    if (e != hipSuccess)
+      return set_error(HSPMV_E_HIP, "x-slab value refresh on GPU %d failed: %s", s.dev.device,
+                       hipGetErrorString(e));
+  }
+  return HSPMV_OK;
+}
+
+int update_values_why(const Shard &s) {
+  if (s.plan.kernel == kCsort)
+    return set_error(HSPMV_E_INVALID,
+                     "the column-sorted kernel's tables cannot take new values (its entries are sorted by "
+                     "column inside each block, and the fixed-point row scales follow the values): create the "
+                     "handle with hspmv_options.csort = -1 or deterministic = 1 to update it in place");
+  return HSPMV_OK;
+}
+
+int update_shard_values(Shard &s, const void *val, bool on_device, bool borrowed) {
+  if (s.A.nnz == 0) return HSPMV_OK;
+  const size_t bytes = dtype_size(s.val_dtype) * (size_t)s.A.nnz;
+  HIP_TRY(hipSetDevice(s.dev.device));
+  hipStream_t st = s.dev.stream;
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const void *src = nullptr;
+  void *staging = nullptr;
+  int rc = HSPMV_OK;
+  if (borrowed) {  // the caller's device array: the one in use, or a new one from now on
+    if (val) s.A.val = val;
+    src = s.A.val;
+  } else if (s.d_val) {
+    HIP_TRY(hipMemcpyAsync(s.d_val, val, bytes, kind, st));
+    src = s.d_val;
+  } else if (on_device) {
+    src = val;
+  } else {
+    if ((rc = s.dev.alloc(&staging, bytes))) return rc;
+    const hipError_t e = hipMemcpyAsync(staging, val, bytes, kind, st);
+    if (e != hipSuccess)
+      rc = set_error(HSPMV_E_HIP, "hipMemcpyAsync of the staged values failed: %s", hipGetErrorString(e));
+    src = staging;
+  }
+  if (rc == HSPMV_OK) rc = refresh_derived(s, src);
+  if (!on_device) {  // the host array is the caller's again on return
+    const hipError_t e = hipStreamSynchronize(st);
+    s.dev.release(staging);
+    if (e != hipSuccess && rc == HSPMV_OK)
+      rc = set_error(HSPMV_E_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+  }
+  return rc;
+}
+
+}  // namespace hspmv

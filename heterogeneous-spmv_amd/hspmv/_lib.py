@@ -30,6 +30,7 @@ FLAG_XCD_REMAP = 1 << 22
 FLAG_COL16 = 1 << 23
 XCD_CHUNK_SHIFT = 24
 GROUPS_SHIFT = 29
+VALUES_DEVICE = 1  # hspmv_update_values: val is a device pointer
 
 E_CODES = {0: "OK", -1: "E_INVALID", -2: "E_IO", -3: "E_NOMEM", -4: "E_HIP",
            -5: "E_RCCL", -6: "E_NODEV", -7: "E_STATE"}
@@ -204,6 +205,8 @@ SIGNATURES = {
                                      C.POINTER(Options), C.c_int]),
     "hspmv_get_dtypes": (C.c_int, [_H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hspmv_values_fit_f32": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
+    "hspmv_update_values": (C.c_int, [_H, _P, C.c_uint]),
+    "hspmv_mm_update_values": (C.c_int, [_H, _P, C.c_uint]),
     "hspmv_set_x": (C.c_int, [_H, _P]),
     "hspmv_bind_x_device": (C.c_int, [_H, _P]),
     "hspmv_bind_y_device": (C.c_int, [_H, _P]),

@@ -391,6 +391,17 @@ def version() -> str:
 
 # ------------------------------------------------------------------ handle
 
+def _check_values(val, nnz: int, dtype) -> np.ndarray:
+    """val as a contiguous (nnz,) array of dtype; ValueError for another shape
+    or a dtype that does not cast ``same_kind`` to it."""
+    val = np.asarray(val)
+    if val.shape != (nnz,):
+        raise ValueError(f"val has shape {val.shape}, expected (nnz,) = ({nnz},)")
+    if not np.can_cast(val.dtype, dtype, casting="same_kind"):
+        raise ValueError(f"val has dtype {val.dtype}, which does not cast to {np.dtype(dtype)}")
+    return np.ascontiguousarray(val, dtype=dtype)
+
+
 class SpMV:
     """One SpMV operator y = A x on one or more GPUs (a libhspmv handle).
 
@@ -507,6 +518,29 @@ class SpMV:
                                         C.byref(opt)), "hspmv_create_ex")
         self._h = h
         return self
+
+    # -- new values, same pattern
+    def update_values(self, val: np.ndarray) -> None:
+        """New matrix values from host memory, in place (hspmv_update_values):
+        ``val`` holds nnz values in A's CSR order and casts to ``value_dtype``;
+        the plan and ``info`` stay, and every later y is bit for bit what a new
+        handle over the new values gives.  ``op.A`` becomes a CsrMatrix of the
+        same pattern arrays with the new values.  ValueError (before any
+        library call) for another shape or a dtype that does not cast."""
+        val = _check_values(val, self.A.nnz, self.value_dtype)
+        check(lib().hspmv_update_values(self._h, _ptr(val), 0), "hspmv_update_values")
+        self.A = CsrMatrix(self.A.m, self.A.n, self.A.row_ptr, self.A.col_idx, val, self.A.index_base)
+
+    def update_values_device(self, ptr: Optional[int]) -> None:
+        """New values from a device array of nnz ``value_dtype`` entries on the
+        handle's device (HSPMV_VALUES_DEVICE; single-device handles), enqueued
+        on the handle's stream with no host synchronisation: the array must
+        stay unchanged until that work is done.  A handle over borrowed arrays
+        (from_device): ``None`` refreshes what the handle derived from the
+        array it borrows, after an in-place change; another pointer is the
+        borrowed array from then on.  ``op.A`` is left as it is: the new values
+        never pass through host memory."""
+        check(lib().hspmv_update_values(self._h, ptr, _lib.VALUES_DEVICE), "hspmv_update_values")
 
     # -- vectors
     def set_x(self, x: np.ndarray) -> None:
@@ -637,6 +671,21 @@ class SpMM:
         self._init_meta(A_meta, k)
         self._create(csr_dev, FLAG_DEVICE_PTRS | (FLAG_NONTEMPORAL if nontemporal else 0), device, stream)
         return self
+
+    # -- new values, same pattern
+    def update_values(self, val: np.ndarray) -> None:
+        """New matrix values from host memory (hspmv_mm_update_values), as
+        :meth:`SpMV.update_values`; ``op.A`` takes the new values."""
+        val = _check_values(val, self.A.nnz, self.dtype)
+        check(lib().hspmv_mm_update_values(self._h, _ptr(val), 0), "hspmv_mm_update_values")
+        self.A = CsrMatrix(self.A.m, self.A.n, self.A.row_ptr, self.A.col_idx, val, self.A.index_base)
+
+    def update_values_device(self, ptr: Optional[int]) -> None:
+        """New values from a device array on the operator's device, copied on
+        its stream (HSPMV_VALUES_DEVICE); an operator over borrowed arrays
+        reads its array on every SpMM: ``None`` does nothing, another pointer
+        is the borrowed array from then on.  ``op.A`` is left as it is."""
+        check(lib().hspmv_mm_update_values(self._h, ptr, _lib.VALUES_DEVICE), "hspmv_mm_update_values")
 
     # -- vectors
     def _check_x(self, X) -> np.ndarray:

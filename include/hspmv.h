@@ -53,8 +53,9 @@ extern "C" {
  * hspmv_set_sweep, hspmv_block_order, hspmv_info.sweep; the multi-vector
  * operator hspmv_mm_* (hspmv_mm, hspmv_mm_info); the mixed-precision handle
  * (fp32 values under fp64 vectors): hspmv_create_mixed, hspmv_get_dtypes,
- * hspmv_values_fit_f32, hspmv_slices_plan_vec -- functions only, no struct
- * grew. */
+ * hspmv_values_fit_f32, hspmv_slices_plan_vec; new values for a planned
+ * handle or operator: hspmv_update_values, hspmv_mm_update_values,
+ * HSPMV_VALUES_DEVICE -- functions only, no struct grew. */
 
 /* ---------------------------------------------------------------- status */
 #define HSPMV_OK 0
@@ -71,12 +72,16 @@ typedef enum { HSPMV_F32 = 0, HSPMV_F64 = 1 } hspmv_dtype;
 
 /* A CSR matrix.  Borrowed: hspmv_create copies host arrays (the caller may
  * free them afterwards).  With HSPMV_FLAG_DEVICE_PTRS the handle REFERENCES
- * the caller's device arrays: they must stay allocated and unchanged for the
- * handle's lifetime -- the row kernels read row_ptr / col_idx / val on every
- * SpMV, and the derived tables built at creation (16-bit columns, x
- * dictionaries, x slabs, column-sorted blocks) are snapshots of col_idx and
- * val, so an in-place update would be used partly or not at all.  Re-create
- * the handle after changing the matrix. */
+ * the caller's device arrays: they must stay allocated for the handle's
+ * lifetime, and row_ptr / col_idx unchanged -- the row kernels read them on
+ * every SpMV, and the tables built at creation (16-bit columns, x
+ * dictionaries, row slices, x slabs) are derived from the pattern.  val may
+ * change: some kernels read it on every SpMV, others read a copy made at
+ * creation (the row slices and the x slabs), so after writing new values into
+ * it -- or to switch to another array -- call hspmv_update_values(h, NULL or
+ * the new array, HSPMV_VALUES_DEVICE), which refreshes every copy; until that
+ * call a changed array is used partly or not at all.  A changed pattern needs
+ * a new handle. */
 typedef struct {
   int64_t m, n, nnz;
   const int32_t *row_ptr; /* m+1 entries, row_ptr[0] == 0                */
@@ -260,8 +265,9 @@ typedef struct hspmv_handle hspmv_handle;
 #define HSPMV_FLAG_NONTEMPORAL (1u << 12) /* nt loads for val/col streams  */
 #define HSPMV_FLAG_DEVICE_PTRS (1u << 13) /* A/maps are device pointers on
                                              the target device (borrowed for
-                                             the handle's lifetime, unchanged;
-                                             see hspmv_csr)                 */
+                                             the handle's lifetime; new values:
+                                             hspmv_update_values, see
+                                             hspmv_csr)                     */
 #define HSPMV_FLAG_NO_XCD_REMAP (1u << 14) /* keep dispatch-order blocks    */
 /* Default (neither XCD flag): remap only when the matrix's bytes fit the
  * 256 MiB Infinity Cache (<= 192 MiB), where per-XCD L2 reuse of x pays;
@@ -469,6 +475,52 @@ int hspmv_create_on_device(hspmv_handle **h, const hspmv_csr *A,
                            const hspmv_csr3_maps *maps, int device,
                            void *stream, unsigned flags);
 
+/* New matrix values for a planned handle, in place: the pattern is the same,
+ * the numbers are not (a Newton or time step, another load case, a refinement
+ * sweep).  val holds nnz values in the CSR order of the matrix the handle was
+ * created from -- for a sharded handle the global matrix -- in the handle's
+ * stored value dtype (hspmv_get_dtypes; fp32 for a mixed handle).  The pattern
+ * (row_ptr, col_idx, the maps) is unchanged by contract; nothing re-validates
+ * it.
+ *
+ * Contract: every later hspmv_spmv / hspmv_run gives bit for bit the y of a
+ * handle newly created with the same arguments and options from the same
+ * pattern with val, on every row and in every supported plan.  The plan, the
+ * tables, hspmv_info (device_bytes included) and the sweep phase are untouched:
+ * only the values move -- into the CSR-order array, and from there, by two
+ * small kernels on the handle's stream, into the row slices' and the x slabs'
+ * own copies.
+ *
+ * flags = 0: val is host memory.  It is consumed before return (hspmv_set_x's
+ * rule); works on single-device and sharded handles, shard p taking its range
+ * of nonzeros.  A row-slice handle, which keeps no CSR-order values, stages
+ * them in a device allocation of nnz values that is released before return.
+ * HSPMV_VALUES_DEVICE: val is a device pointer on the handle's device;
+ * single-device handles only.  Everything is enqueued on the handle's stream,
+ * after the SpMVs enqueued so far and before later ones, with no host
+ * synchronisation and no allocation; val must stay unchanged until that stream
+ * work is done.
+ * A handle over borrowed arrays (HSPMV_FLAG_DEVICE_PTRS) takes
+ * HSPMV_VALUES_DEVICE only: val == NULL means "I changed my array in place,
+ * refresh what you derived from it"; another pointer is the borrowed array
+ * from then on.
+ *
+ * HSPMV_E_INVALID, the handle unchanged (every check is made, for every shard,
+ * before anything is written): a NULL handle, unknown flag bits, a NULL val
+ * on a handle that owns its matrix (nnz > 0), host memory for a borrowed
+ * handle, HSPMV_VALUES_DEVICE on a sharded handle, and a handle any shard of
+ * which runs the column-sorted kernel (hspmv_info.kernel ==
+ * HSPMV_KERNEL_CSORT) -- create it with hspmv_options.csort = -1 or
+ * deterministic = 1 to update it.  nnz == 0: HSPMV_OK, nothing done.
+ *
+ * Not covered: column-sorted handles (their entries are sorted by column
+ * inside each block, which only a stored source index per entry could undo,
+ * and the fixed-point row scales follow the values); converting the dtype on
+ * the way (fp64 input into a mixed handle: narrow it first); a changed
+ * pattern; device pointers for sharded handles. */
+#define HSPMV_VALUES_DEVICE 1u  /* val is a device pointer on the handle's device */
+int hspmv_update_values(hspmv_handle *h, const void *val, unsigned flags);
+
 /* x (n entries of dtype) from host memory -> every GPU (setX, csrk.cu:92-102,
  * minus the x permutation: matrices are used as given). */
 int hspmv_set_x(hspmv_handle *h, const void *x_host);
@@ -579,6 +631,16 @@ typedef struct {
 } hspmv_mm_info;
 
 int hspmv_mm_create(hspmv_mm **mm, const hspmv_csr *A, int32_t k, const hspmv_options *opt);
+/* hspmv_update_values for the operator, which keeps plain CSR: nnz values of
+ * A's dtype in CSR order, from host memory (flags = 0; consumed before return)
+ * or a device pointer (HSPMV_VALUES_DEVICE; a copy on the operator's stream,
+ * ordered with its SpMMs) into the operator's own values.  An operator over
+ * borrowed arrays reads the caller's val on every SpMM, so it takes
+ * HSPMV_VALUES_DEVICE only: NULL is accepted and does nothing, another pointer
+ * is the borrowed array from then on.  HSPMV_E_INVALID: a NULL operator,
+ * unknown flag bits, a NULL val on an owned operator (nnz > 0), host memory
+ * for a borrowed one. */
+int hspmv_mm_update_values(hspmv_mm *mm, const void *val, unsigned flags);
 /* X (row-major n x k, ldx >= k) from host memory into the operator's own
  * buffer, which becomes the X in use. */
 int hspmv_mm_set_x(hspmv_mm *mm, const void *X_host, int64_t ldx);
