@@ -30,6 +30,9 @@ namespace hspmv {
 // HSPMV_KERNEL_CSORT forces it, Tuning.csort = -1 turns auto off,
 // Tuning.csort_parts = 1/2/4 sets the column parts, csort_u = 4/8/16 the
 // chunk.  The row blocks are capped by the device's LDS per workgroup.
+// plan_csort builds the tables on the host, one stage per function below, in
+// the order they run; upload_csort puts a plan on the device; build_csort
+// asks the device for its limits and runs the two.
 constexpr int32_t kCsortSlice = 2048;
 // a chunk whose instructions would serialise more than this many same-slot
 // lanes in all is stored slot-sorted (segmented)
@@ -42,6 +45,12 @@ constexpr double kSweepPerRowBlock = 0.13;  // a column's sweep cost, in entries
 // part median of 85 with the same entries and 100-160 segmented chunks
 // (profiles/r04/csort_trace_wg_cost_balanced.jsonl): ~1.6x per entry.
 constexpr int32_t kWUnit = 16, kWCrowded = 26;
+// diagnostic builds (Tuning.csort_trace): per workgroup {rows, slices,
+// chunks, entries, gather quad-sectors, gather sectors, segmented chunks,
+// 0} -- the cost terms the per-workgroup timelines are compared with
+constexpr int kWgStats = 8;
+
+namespace {
 
 struct CsEnt {
   uint32_t col, slot, k;
@@ -50,64 +59,81 @@ struct CsEnt {
   }
 };
 
-int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
-                int64_t n, int dtype, unsigned flags) {
-  if (m == 0 || n == 0 || !val) return HSPMV_OK;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s.dev.device) != hipSuccess ||
-      cus <= 0)
-    cus = 256;
-  int lds_max = 0;  // the row slots must fit one workgroup's LDS on THIS device
-  if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, s.dev.device) != hipSuccess ||
-      lds_max <= 0)
-    return HSPMV_OK;
-  // the kernel's static LDS (its chunk-queue head, 16 B with alignment)
-  // comes out of the same budget
-  lds_max = std::min(lds_max, kCsortMaxLds) - 16;
-  const Tuning &tn = s.tune;
-  if (tn.csort_lds_cap > 0) lds_max = std::min(lds_max, tn.csort_lds_cap);  // A/B
-  const bool slot32 = dtype == HSPMV_F32 && tn.csort_slot32 == 1;
-  const int64_t slot_bytes = slot32 ? 4 : 8;
-  const int32_t max_slots = (int32_t)(lds_max / slot_bytes) - 1;
-  int H = n >= 2 ? 2 : 1;
+// the shard's host CSR
+struct Csr {
+  const int32_t *rp, *col;
+  const void *val;
+  int64_t m, n;
+  int dtype;
+};
+
+// What the dtype, the knobs and the device's limits fix before a table is built.
+struct Shape {
+  int H = 1, U = 8;   // column parts; entries per lane and chunk
+  int64_t C = 0;      // entries per chunk, 64 * U
+  bool slot32 = false, wide = false;
+  int64_t slot_bytes = 8;
+  int32_t lds_max = 0, max_slots = 0;  // the row slots' LDS on this device
+  int32_t long_t = 0;                  // rows above this many nonzeros are long rows
+  int64_t nb0 = 1;                     // row blocks per column part, at most
+};
+
+Shape csort_shape(const Csr &A, unsigned flags, const Tuning &tn, const CsortLimits &lim) {
+  Shape S;
+  S.lds_max = lim.lds_bytes;
+  if (tn.csort_lds_cap > 0) S.lds_max = std::min(S.lds_max, tn.csort_lds_cap);  // A/B
+  S.slot32 = A.dtype == HSPMV_F32 && tn.csort_slot32 == 1;
+  S.slot_bytes = S.slot32 ? 4 : 8;
+  S.max_slots = (int32_t)(S.lds_max / S.slot_bytes) - 1;
+  S.H = A.n >= 2 ? 2 : 1;
   if (tn.csort_parts == 1 || tn.csort_parts == 2 || tn.csort_parts == 4)
-    H = (int)std::min<int64_t>(tn.csort_parts, n);
-  int U = dtype == HSPMV_F32 ? 16 : 8;
-  if (tn.csort_u == 4 || tn.csort_u == 8 || tn.csort_u == 16) U = tn.csort_u;
+    S.H = (int)std::min<int64_t>(tn.csort_parts, A.n);
+  S.U = A.dtype == HSPMV_F32 ? 16 : 8;
+  if (tn.csort_u == 4 || tn.csort_u == 8 || tn.csort_u == 16) S.U = tn.csort_u;
   const int bpc = tn.csort_blocks_per_cu > 0 ? std::min(tn.csort_blocks_per_cu, 8) : 1;
   // 16-byte entry loads: needs U a multiple of 2 (fp32 records) / 4 (fp64 indices)
   // 16-byte entry loads + the next chunk's entries loaded during this chunk's
   // gathers: fp32 C5 107 -> 103 us, RCM'd C5 192 -> 190, in four one-process
   // A/Bs (profiles/r03/ab_c5_wide_pf*.jsonl); fp64 keeps 8-byte loads
   // (unmeasured).  Neither alone moves C5 (wide 108.8 vs 108.0, PF 109.4).
-  const bool wide_default = dtype == HSPMV_F32;
-  const bool wide = (tn.csort_wide >= 0 ? tn.csort_wide == 1 : wide_default) &&
-                    (dtype == HSPMV_F32 ? U % 2 == 0 : U % 4 == 0);
-  const int64_t C = 64 * U;
-  const size_t sv = dtype_size(dtype);
-  const int32_t long_t =
-      s.tune.csort_long > 0 && !(flags & HSPMV_FLAG_NO_SPLIT) ? s.tune.csort_long : split_threshold(flags);
-  const int64_t nb0 = std::max<int64_t>(1, (int64_t)cus * bpc / H);
-  // Column parts: [pb[h], pb[h+1]).  Equal widths, or (Tuning.csort_balance
-  // >= 0, the default) boundaries at equal shares of the parts' COST, each
-  // part's width kept within kPartSlack of n / H.  A workgroup's time is
-  // ~alpha per entry + beta per column of its part (the x sweep): from the
-  // per-workgroup timelines of c5r (profiles/r04c/csort_trace_wg*.jsonl),
-  // alpha = 2.5e-4 us, beta = 3.0-3.4e-5 us per fp32 column, so a column
-  // weighs kSweepPerRowBlock * (row blocks) entries (x 2 * 8 / 12 for fp64
-  // x and entries).  An RCM ordering concentrates a power-law matrix's
-  // entries in the upper columns (c5r: 59 % in the upper half): equal widths
-  // gave that half's workgroups 1.42x the entries (123.4 us), equal entries
-  // over-corrected onto the wider lower part (108.8 us, its sweep 43 % wider).
-  std::vector<int64_t> pb((size_t)H + 1, 0);
-  for (int h = 0; h <= H; ++h) pb[(size_t)h] = (n * h + H - 1) / H;  // c in part floor(c*H/n)
+  const bool wide_default = A.dtype == HSPMV_F32;
+  S.wide = (tn.csort_wide >= 0 ? tn.csort_wide == 1 : wide_default) &&
+           (A.dtype == HSPMV_F32 ? S.U % 2 == 0 : S.U % 4 == 0);
+  S.C = 64 * S.U;
+  S.long_t = tn.csort_long > 0 && !(flags & HSPMV_FLAG_NO_SPLIT) ? tn.csort_long : split_threshold(flags);
+  S.nb0 = std::max<int64_t>(1, (int64_t)lim.cus * bpc / S.H);
+  return S;
+}
+
+struct ColParts {
+  std::vector<int64_t> pb;   // part h: columns [pb[h], pb[h+1])
+  std::vector<uint8_t> tab;  // column -> part (empty for one part)
+  int of(int64_t c) const { return tab.empty() ? 0 : (int)tab[(size_t)c]; }
+};
+
+// Column parts: [pb[h], pb[h+1]).  Equal widths, or (Tuning.csort_balance
+// >= 0, the default) boundaries at equal shares of the parts' COST, each
+// part's width kept within kPartSlack of n / H.  A workgroup's time is
+// ~alpha per entry + beta per column of its part (the x sweep): from the
+// per-workgroup timelines of c5r (profiles/r04c/csort_trace_wg*.jsonl),
+// alpha = 2.5e-4 us, beta = 3.0-3.4e-5 us per fp32 column, so a column
+// weighs kSweepPerRowBlock * (row blocks) entries (x 2 * 8 / 12 for fp64
+// x and entries).  An RCM ordering concentrates a power-law matrix's
+// entries in the upper columns (c5r: 59 % in the upper half): equal widths
+// gave that half's workgroups 1.42x the entries (123.4 us), equal entries
+// over-corrected onto the wider lower part (108.8 us, its sweep 43 % wider).
+ColParts column_parts(const Csr &A, const Shape &S, const Tuning &tn) {
+  const int H = S.H;
+  const int64_t n = A.n;
+  ColParts P;
+  P.pb.assign((size_t)H + 1, 0);
+  for (int h = 0; h <= H; ++h) P.pb[(size_t)h] = (n * h + H - 1) / H;  // c in part floor(c*H/n)
   if (H > 1 && tn.csort_balance >= 0) {
     std::vector<int64_t> colcnt((size_t)n + 1, 0);
-    for (int64_t k = 0; k < rp[m]; ++k) ++colcnt[(size_t)col[k]];
-    const double nb_part = (double)std::max<int64_t>(1, (int64_t)cus * bpc / H);
+    for (int64_t k = 0; k < A.rp[A.m]; ++k) ++colcnt[(size_t)A.col[k]];
     const double wsw = tn.csort_sweep_w > 0 ? tn.csort_sweep_w : kSweepPerRowBlock;
-    const double wcol = wsw * nb_part * (dtype == HSPMV_F64 ? 2.0 * 8.0 / 12.0 : 1.0);
-    const double tot = (double)rp[m] + wcol * (double)n;
+    const double wcol = wsw * (double)S.nb0 * (A.dtype == HSPMV_F64 ? 2.0 * 8.0 / 12.0 : 1.0);
+    const double tot = (double)A.rp[A.m] + wcol * (double)n;
     double acc = 0.0;
     int64_t c = 0;
     for (int h = 1; h < H; ++h) {
@@ -116,423 +142,581 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
       const int64_t eq = (n * h + H - 1) / H;
       const double ps = tn.csort_slack > 1.0 ? tn.csort_slack : kPartSlack;  // A/B knob
       const int64_t slack = (int64_t)((ps - 1.0) * (double)(n / H));
-      const int64_t lo = std::max(pb[(size_t)h - 1] + 1, eq - slack), hi = std::max(lo, eq + slack);
-      pb[(size_t)h] = std::min(std::max(c, lo), hi);
+      const int64_t lo = std::max(P.pb[(size_t)h - 1] + 1, eq - slack), hi = std::max(lo, eq + slack);
+      P.pb[(size_t)h] = std::min(std::max(c, lo), hi);
     }
   }
-  std::vector<uint8_t> part_tab;
   if (H > 1) {
-    part_tab.assign((size_t)n, 0);
+    P.tab.assign((size_t)n, 0);
     for (int h = 0; h < H; ++h)
-      std::fill(part_tab.begin() + pb[(size_t)h], part_tab.begin() + pb[(size_t)h + 1], (uint8_t)h);
+      std::fill(P.tab.begin() + P.pb[(size_t)h], P.tab.begin() + P.pb[(size_t)h + 1], (uint8_t)h);
   }
-  auto part_of = [&](int64_t c) { return H > 1 ? (int)part_tab[(size_t)c] : 0; };
-  // long rows and their slices (per part, kCsortSlice nonzeros each)
-  std::vector<int32_t> lrow, lcs(1, 0);
+  return P;
+}
+
+// long rows and their slices (per part, kCsortSlice nonzeros each)
+struct LongRows {
+  std::vector<int32_t> row, cs{0};             // the rows; row j's slices [cs[j], cs[j+1])
   std::vector<std::vector<uint32_t>> slice_k;  // source nonzeros per slice
   std::vector<int> slice_part;
-  int64_t long_nnz = 0;
-  for (int64_t r = 0; r < m; ++r) {
-    const int32_t k0 = rp[r], k1 = rp[r + 1];
-    if (k1 - k0 <= long_t) continue;
-    long_nnz += k1 - k0;
-    lrow.push_back((int32_t)r);
-    std::vector<std::vector<uint32_t>> byp((size_t)H);
-    for (int32_t k = k0; k < k1; ++k) byp[(size_t)part_of(col[k])].push_back((uint32_t)k);
-    for (int h = 0; h < H; ++h)
+  std::vector<int32_t> slice_row;
+  int64_t n_slices() const { return (int64_t)slice_k.size(); }
+};
+
+LongRows long_rows(const Csr &A, const Shape &S, const ColParts &P) {
+  LongRows L;
+  for (int64_t r = 0; r < A.m; ++r) {
+    const int32_t k0 = A.rp[r], k1 = A.rp[r + 1];
+    if (k1 - k0 <= S.long_t) continue;
+    L.row.push_back((int32_t)r);
+    std::vector<std::vector<uint32_t>> byp((size_t)S.H);
+    for (int32_t k = k0; k < k1; ++k) byp[(size_t)P.of(A.col[k])].push_back((uint32_t)k);
+    for (int h = 0; h < S.H; ++h)
       for (size_t i = 0; i < byp[(size_t)h].size(); i += kCsortSlice) {
         const size_t e = std::min(byp[(size_t)h].size(), i + kCsortSlice);
-        slice_k.emplace_back(byp[(size_t)h].begin() + (ptrdiff_t)i, byp[(size_t)h].begin() + (ptrdiff_t)e);
-        slice_part.push_back(h);
+        L.slice_k.emplace_back(byp[(size_t)h].begin() + (ptrdiff_t)i, byp[(size_t)h].begin() + (ptrdiff_t)e);
+        L.slice_part.push_back(h);
+        L.slice_row.push_back((int32_t)r);
       }
-    lcs.push_back((int32_t)slice_k.size());
+    L.cs.push_back((int32_t)L.slice_k.size());
   }
-  const int64_t n_slices = (int64_t)slice_k.size();
-  // Reproducible (fixed-point) slots (Tuning.deterministic == 2, csort.hip
-  // fix_q): every value of row r is stored scaled by 2^rexp[r], exactly (a
-  // power of two), so that the row's |v'| < 2^-extra: rexp = -(ilogb max|v| +
-  // 1) - extra, extra = ceil(log2 len) - 12 for a row kept whole over 4096
-  // nonzeros (HSPMV_FLAG_NO_SPLIT), else 0 -- every product then rounds to an
-  // integer below 2^kCsortFixBits and a slot of <= 4096 of them stays below
-  // 2^62.  A value that the scaling takes below the type's normal range loses
-  // bits only below the products' rounding unit (2^-kCsortFixBits of the
-  // row's largest).
-  // A matrix with an Inf or NaN value has no fixed-point scale for its row
-  // (the product must stay non-finite): such a handle keeps fp64 slots and
-  // reports csort_fixed_point = 0, deterministic = 0.
-  bool fixed = tn.deterministic == 2 && !slot32;
-  std::vector<int16_t> rexp(fixed ? (size_t)m : 0, 0), sexp;
-  if (fixed) {
-    for (int64_t r = 0; r < m && fixed; ++r) {
-      double mx = 0.0;
-      for (int32_t k = rp[r]; k < rp[r + 1]; ++k) {
-        const double v = dtype == HSPMV_F32 ? (double)static_cast<const float *>(val)[k]
-                                            : static_cast<const double *>(val)[k];
-        mx = std::max(mx, std::fabs(v));
-        if (!std::isfinite(v)) fixed = false;
+  return L;
+}
+
+// Reproducible (fixed-point) slots (Tuning.deterministic == 2, csort.hip
+// fix_q): every value of row r is stored scaled by 2^rexp[r], exactly (a
+// power of two), so that the row's |v'| < 2^-extra: rexp = -(ilogb max|v| +
+// 1) - extra, extra = ceil(log2 len) - 12 for a row kept whole over 4096
+// nonzeros (HSPMV_FLAG_NO_SPLIT), else 0 -- every product then rounds to an
+// integer below 2^kCsortFixBits and a slot of <= 4096 of them stays below
+// 2^62.  A value that the scaling takes below the type's normal range loses
+// bits only below the products' rounding unit (2^-kCsortFixBits of the
+// row's largest).
+// A matrix with an Inf or NaN value has no fixed-point scale for its row
+// (the product must stay non-finite): such a handle keeps fp64 slots and
+// reports csort_fixed_point = 0, deterministic = 0.
+// rexp per row and sexp per slice (its row's); false, both empty, for such a matrix.
+bool row_scales(const Csr &A, int32_t long_t, const LongRows &L, std::vector<int16_t> &rexp,
+                std::vector<int16_t> &sexp) {
+  rexp.assign((size_t)A.m, 0);
+  for (int64_t r = 0; r < A.m; ++r) {
+    double mx = 0.0;
+    for (int32_t k = A.rp[r]; k < A.rp[r + 1]; ++k) {
+      const double v = A.dtype == HSPMV_F32 ? (double)static_cast<const float *>(A.val)[k]
+                                            : static_cast<const double *>(A.val)[k];
+      mx = std::max(mx, std::fabs(v));
+      if (!std::isfinite(v)) {
+        std::vector<int16_t>().swap(rexp);
+        return false;
       }
-      if (!(mx > 0.0) || !std::isfinite(mx)) continue;  // empty / zero rows
-      const int64_t len = rp[r + 1] - rp[r];
-      int extra = 0;  // (a sliced row's slots hold kCsortSlice <= 4096 products each)
-      while (len <= long_t && ((int64_t)4096 << extra) < len) ++extra;
-      rexp[(size_t)r] = (int16_t)(-(std::ilogb(mx) + 1) - extra);
     }
-    if (!fixed) std::vector<int16_t>().swap(rexp);
+    if (!(mx > 0.0)) continue;  // empty / zero rows
+    const int64_t len = A.rp[r + 1] - A.rp[r];
+    int extra = 0;  // (a sliced row's slots hold kCsortSlice <= 4096 products each)
+    while (len <= long_t && ((int64_t)4096 << extra) < len) ++extra;
+    rexp[(size_t)r] = (int16_t)(-(std::ilogb(mx) + 1) - extra);
   }
-  if (fixed) {
-    sexp.resize((size_t)std::max<int64_t>(n_slices, 1), 0);
-    for (size_t j = 0; j + 1 < lcs.size(); ++j)
-      for (int32_t sl = lcs[j]; sl < lcs[j + 1]; ++sl) sexp[(size_t)sl] = rexp[(size_t)lrow[j]];
-  }
-  // the (scaled) value of nonzero k of row r
-  auto value_f32 = [&](uint32_t k, int64_t r) -> uint32_t {
+  sexp.assign((size_t)std::max<int64_t>(L.n_slices(), 1), 0);
+  for (int64_t sl = 0; sl < L.n_slices(); ++sl) sexp[(size_t)sl] = rexp[(size_t)L.slice_row[(size_t)sl]];
+  return true;
+}
+
+// the (scaled) value of nonzero k of row r; rexp: null unless fixed-point
+struct Values {
+  const void *val;
+  const int16_t *rexp;
+  uint32_t f32(uint32_t k, int64_t r) const {
     float v = static_cast<const float *>(val)[k];
-    if (fixed) v = std::ldexp(v, rexp[(size_t)r]);
+    if (rexp) v = std::ldexp(v, rexp[r]);
     uint32_t b;
     memcpy(&b, &v, 4);
     return b;
-  };
-  auto value_f64 = [&](uint32_t k, int64_t r) -> double {
+  }
+  double f64(uint32_t k, int64_t r) const {
     const double v = static_cast<const double *>(val)[k];
-    return fixed ? std::ldexp(v, rexp[(size_t)r]) : v;
-  };
-  // Row blocks PER COLUMN PART.  Part h is a fixed slice of x, [pb[h],
-  // pb[h+1]) (above), and workgroup j works on part
-  // j % H: under round-robin dispatch (workgroup j on XCD j % 8;
-  // tools/xcd_map_probe.hip records it per box) every XCD sweeps one slice,
-  // which its 4 MiB L2 keeps for all its CUs.  Each part has its OWN row
-  // partition, balanced on the nonzeros that fall in that part and capped in
-  // rows (the LDS slots), so the parts' workgroups carry equal work whatever
-  // the ordering: with one row partition for all parts an RCM-ordered
-  // power-law matrix put ~90 % of a block's entries in one part (322 us vs
-  // 108 us on the same matrix unordered), and quantile splits per block, which
-  // balance the work but let every XCD sweep all of x, still took 205 us.
-  const int64_t reserve = n_slices / nb0 + 2;
-  const int64_t row_cap = max_slots - 1 - reserve;
-  if (row_cap < 64) return HSPMV_OK;  // too many slices for the LDS: not this path
-  // [h][r]: row r's in-kernel nonzeros in part h, then its partition weight
+    return rexp ? std::ldexp(v, rexp[r]) : v;
+  }
+};
+
+// [h][r]: the partition weight of row r's in-kernel nonzeros in part h
+std::vector<int32_t> row_weights(const Csr &A, const Shape &S, const ColParts &P, const Tuning &tn) {
+  const int H = S.H;
+  const int64_t m = A.m;
+  const int32_t *rp = A.rp, *col = A.col;
   std::vector<int32_t> cnt((size_t)(H * m), 0);
-  std::vector<int64_t> tot_part((size_t)H, 0);
   parallel_ranges(m, 65536, [&](int64_t r0, int64_t r1, int) {
     for (int64_t r = r0; r < r1; ++r) {
-      if (rp[r + 1] - rp[r] > long_t) continue;
-      for (int32_t k = rp[r]; k < rp[r + 1]; ++k) ++cnt[(size_t)(part_of(col[k]) * m + r)];
+      if (rp[r + 1] - rp[r] > S.long_t) continue;
+      for (int32_t k = rp[r]; k < rp[r + 1]; ++k) ++cnt[(size_t)(P.of(col[k]) * m + r)];
     }
   });
-  for (int h = 0; h < H; ++h)
-    for (int64_t r = 0; r < m; ++r) tot_part[(size_t)h] += cnt[(size_t)(h * m + r)];
   // a row's partition weight (int32: a row of > 2^31 / kWCrowded entries,
   // possible only unsplit, saturates)
   auto weigh = [](int64_t plain, int64_t crowded) {
     return (int32_t)std::min<int64_t>(INT32_MAX / 2, plain * kWUnit + crowded * kWCrowded);
   };
-  if (tn.csort_balance >= 0) {
-    // Crowded entries: ones with >= kCsortSegHeavy entries of the same row
-    // within the columns one chunk of a block covers (cspan) -- the entries
-    // that make their chunks segmented.  An RCM ordering clusters a hub
-    // row's columns, so the row's whole span says little: each entry's own
-    // window is counted (sorted copy of the row's part, two pointers).
-    std::vector<double> cspan((size_t)H, 0.0);
-    for (int h = 0; h < H; ++h)
-      cspan[(size_t)h] = tot_part[(size_t)h] ? (double)C * (double)(pb[(size_t)h + 1] - pb[(size_t)h]) *
-                                                   (double)nb0 / (double)tot_part[(size_t)h]
-                                             : 0.0;
-    parallel_ranges(m, 65536, [&](int64_t r0, int64_t r1, int) {
-      std::vector<int32_t> cs;
-      std::vector<int32_t> crowded((size_t)H);
-      for (int64_t r = r0; r < r1; ++r) {
-        const int32_t len = rp[r + 1] - rp[r];
-        if (len > long_t || len < kCsortSegHeavy) {
-          for (int h = 0; h < H; ++h) cnt[(size_t)(h * m + r)] = weigh(cnt[(size_t)(h * m + r)], 0);
-          continue;
-        }
-        cs.assign(col + rp[r], col + rp[r + 1]);
-        std::sort(cs.begin(), cs.end());
-        std::fill(crowded.begin(), crowded.end(), 0);
-        for (size_t i = 0, j = 0; i < cs.size(); ++i) {  // entries i..j-1 within cspan of cs[i]
-          const int h = part_of(cs[i]);
-          const double lim = (double)cs[i] + cspan[(size_t)h];
-          if (j < i + 1) j = i + 1;
-          while (j < cs.size() && (double)cs[j] < lim && part_of(cs[j]) == h) ++j;
-          if ((int64_t)(j - i) >= kCsortSegHeavy) ++crowded[(size_t)h];
-        }
-        for (int h = 0; h < H; ++h) {
-          const size_t i = (size_t)(h * m + r);
-          const int32_t cr = std::min(cnt[i], crowded[(size_t)h]);
-          cnt[i] = weigh(cnt[i] - cr, cr);
-        }
-      }
-    });
-  } else {
+  if (tn.csort_balance < 0) {
     for (auto &v : cnt) v = weigh(v, 0);
+    return cnt;
   }
-  // Greedy cuts at `target` weight or row_cap rows; the target is the
-  // smallest that yields at most nb0 blocks (one block more would run a
-  // second round of workgroups on one CU and double the launch).
-  auto cut_w = [&](const int32_t *c, int64_t target, std::vector<int32_t> *out) -> int64_t {
-    int64_t start = 0, acc = 0, nblk = 1;
-    if (out) out->assign(1, 0);
-    for (int64_t r = 0; r < m; ++r) {
-      if (r > start && (r - start >= row_cap || acc >= target)) {
-        if (out) out->push_back((int32_t)r);
-        ++nblk;
-        start = r;
-        acc = 0;
-      }
-      acc += c[r];
-    }
-    if (out) out->push_back((int32_t)m);
-    return nblk;
-  };
-  // the smallest target giving at most nb0 blocks
-  auto partition = [&](const int32_t *c, std::vector<int32_t> &out) {
-    int64_t tot_h = 0;
-    for (int64_t r = 0; r < m; ++r) tot_h += c[r];
-    int64_t lo = std::max<int64_t>(1, (tot_h + nb0 - 1) / nb0), hi = std::max<int64_t>(lo, tot_h + 1);
-    if (cut_w(c, lo, nullptr) > nb0) {
-      if (cut_w(c, hi, nullptr) > nb0) lo = hi;  // the row cap alone needs more blocks
-      while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (cut_w(c, mid, nullptr) <= nb0) hi = mid; else lo = mid + 1;
-      }
-    }
-    cut_w(c, lo, &out);
-  };
-  std::vector<std::vector<int32_t>> brh((size_t)H);
-  int64_t NB = 0;
+  // Crowded entries: ones with >= kCsortSegHeavy entries of the same row
+  // within the columns one chunk of a block covers (cspan) -- the entries
+  // that make their chunks segmented.  An RCM ordering clusters a hub
+  // row's columns, so the row's whole span says little: each entry's own
+  // window is counted (sorted copy of the row's part, two pointers).
+  std::vector<double> cspan((size_t)H, 0.0);
   for (int h = 0; h < H; ++h) {
-    partition(cnt.data() + (size_t)h * (size_t)m, brh[(size_t)h]);
-    NB = std::max<int64_t>(NB, (int64_t)brh[(size_t)h].size() - 1);
+    int64_t tot = 0;
+    for (int64_t r = 0; r < m; ++r) tot += cnt[(size_t)(h * m + r)];
+    cspan[(size_t)h] =
+        tot ? (double)S.C * (double)(P.pb[(size_t)h + 1] - P.pb[(size_t)h]) * (double)S.nb0 / (double)tot : 0.0;
   }
-  std::vector<int32_t>().swap(cnt);
-  const int64_t G = NB * H;
-  if (G >= INT32_MAX) return HSPMV_OK;
-  // workgroup j: part j % H, that part's block j / H (empty past its blocks)
-  std::vector<int32_t> wg_rows((size_t)(2 * G), (int32_t)m);
+  parallel_ranges(m, 65536, [&](int64_t r0, int64_t r1, int) {
+    std::vector<int32_t> cs;
+    std::vector<int32_t> crowded((size_t)H);
+    for (int64_t r = r0; r < r1; ++r) {
+      const int32_t len = rp[r + 1] - rp[r];
+      if (len > S.long_t || len < kCsortSegHeavy) {
+        for (int h = 0; h < H; ++h) cnt[(size_t)(h * m + r)] = weigh(cnt[(size_t)(h * m + r)], 0);
+        continue;
+      }
+      cs.assign(col + rp[r], col + rp[r + 1]);
+      std::sort(cs.begin(), cs.end());
+      std::fill(crowded.begin(), crowded.end(), 0);
+      for (size_t i = 0, j = 0; i < cs.size(); ++i) {  // entries i..j-1 within cspan of cs[i]
+        const int h = P.of(cs[i]);
+        const double lim = (double)cs[i] + cspan[(size_t)h];
+        if (j < i + 1) j = i + 1;
+        while (j < cs.size() && (double)cs[j] < lim && P.of(cs[j]) == h) ++j;
+        if ((int64_t)(j - i) >= kCsortSegHeavy) ++crowded[(size_t)h];
+      }
+      for (int h = 0; h < H; ++h) {
+        const size_t i = (size_t)(h * m + r);
+        const int32_t cr = std::min(cnt[i], crowded[(size_t)h]);
+        cnt[i] = weigh(cnt[i] - cr, cr);
+      }
+    }
+  });
+  return cnt;
+}
+
+// Greedy cuts of the m rows weighing c[r] at `target` weight or row_cap
+// rows: the number of blocks, their first rows (and m) into *out.
+int64_t cut_w(const int32_t *c, int64_t m, int64_t row_cap, int64_t target, std::vector<int32_t> *out) {
+  int64_t start = 0, acc = 0, nblk = 1;
+  if (out) out->assign(1, 0);
+  for (int64_t r = 0; r < m; ++r) {
+    if (r > start && (r - start >= row_cap || acc >= target)) {
+      if (out) out->push_back((int32_t)r);
+      ++nblk;
+      start = r;
+      acc = 0;
+    }
+    acc += c[r];
+  }
+  if (out) out->push_back((int32_t)m);
+  return nblk;
+}
+
+// One part's row blocks: the target is the smallest that yields at most nb0
+// blocks (one block more would run a second round of workgroups on one CU
+// and double the launch).
+void partition_rows(const int32_t *c, int64_t m, int64_t row_cap, int64_t nb0, std::vector<int32_t> &out) {
+  int64_t tot_h = 0;
+  for (int64_t r = 0; r < m; ++r) tot_h += c[r];
+  int64_t lo = std::max<int64_t>(1, (tot_h + nb0 - 1) / nb0), hi = std::max<int64_t>(lo, tot_h + 1);
+  if (cut_w(c, m, row_cap, lo, nullptr) > nb0) {
+    if (cut_w(c, m, row_cap, hi, nullptr) > nb0) lo = hi;  // the row cap alone needs more blocks
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if (cut_w(c, m, row_cap, mid, nullptr) <= nb0) hi = mid; else lo = mid + 1;
+    }
+  }
+  cut_w(c, m, row_cap, lo, &out);
+}
+
+// Row blocks PER COLUMN PART.  Part h is a fixed slice of x, [pb[h],
+// pb[h+1]) (above), and workgroup j works on part
+// j % H: under round-robin dispatch (workgroup j on XCD j % 8;
+// tools/xcd_map_probe.hip records it per box) every XCD sweeps one slice,
+// which its 4 MiB L2 keeps for all its CUs.  Each part has its OWN row
+// partition, balanced on the nonzeros that fall in that part and capped in
+// rows (the LDS slots), so the parts' workgroups carry equal work whatever
+// the ordering: with one row partition for all parts an RCM-ordered
+// power-law matrix put ~90 % of a block's entries in one part (322 us vs
+// 108 us on the same matrix unordered), and quantile splits per block, which
+// balance the work but let every XCD sweep all of x, still took 205 us.
+// [h]: the first rows of part h's blocks, and m.
+std::vector<std::vector<int32_t>> row_blocks(const Csr &A, const Shape &S, const ColParts &P, const Tuning &tn,
+                                             int64_t row_cap) {
+  std::vector<std::vector<int32_t>> brh((size_t)S.H);
+  const std::vector<int32_t> cnt = row_weights(A, S, P, tn);  // (released on return: before the entries are sorted)
+  for (int h = 0; h < S.H; ++h)
+    partition_rows(cnt.data() + (size_t)h * (size_t)A.m, A.m, row_cap, S.nb0, brh[(size_t)h]);
+  return brh;
+}
+
+// workgroup j: part j % H, that part's block j / H (empty past its blocks)
+struct WgMap {
+  std::vector<int32_t> rows;             // [2j], [2j+1]: its rows
+  std::vector<std::vector<int32_t>> sl;  // its long-row slices
+};
+
+WgMap deal_workgroups(const std::vector<std::vector<int32_t>> &brh, int64_t G, int64_t m, const LongRows &L) {
+  const int64_t H = (int64_t)brh.size();
+  WgMap W;
+  W.rows.assign((size_t)(2 * G), (int32_t)m);
   for (int64_t j = 0; j < G; ++j) {
     const auto &b = brh[(size_t)(j % H)];
     const int64_t i = j / H;
     if (i + 1 < (int64_t)b.size()) {
-      wg_rows[(size_t)(2 * j)] = b[(size_t)i];
-      wg_rows[(size_t)(2 * j + 1)] = b[(size_t)i + 1];
+      W.rows[(size_t)(2 * j)] = b[(size_t)i];
+      W.rows[(size_t)(2 * j + 1)] = b[(size_t)i + 1];
     }
   }
   // slices dealt round-robin over the blocks of their part
-  std::vector<std::vector<int32_t>> wg_sl((size_t)G);
-  {
-    std::vector<int64_t> next((size_t)H, 0);
-    for (int64_t sl = 0; sl < n_slices; ++sl) {
-      const int h = slice_part[(size_t)sl];
-      const int64_t nbh = (int64_t)brh[(size_t)h].size() - 1;
-      const int64_t i = next[(size_t)h]++ % nbh;
-      wg_sl[(size_t)(i * H + h)].push_back((int32_t)sl);
-    }
+  W.sl.resize((size_t)G);
+  std::vector<int64_t> next((size_t)H, 0);
+  for (int64_t sl = 0; sl < L.n_slices(); ++sl) {
+    const int h = L.slice_part[(size_t)sl];
+    const int64_t nbh = (int64_t)brh[(size_t)h].size() - 1;
+    const int64_t i = next[(size_t)h]++ % nbh;
+    W.sl[(size_t)(i * H + h)].push_back((int32_t)sl);
   }
-  // per workgroup: sorted entries, chunk count (pass 1)
-  std::vector<std::vector<CsEnt>> ents((size_t)G);
-  std::vector<int64_t> nchunks((size_t)G, 0);
-  std::vector<int32_t> nslots((size_t)G, 0);
+  return W;
+}
+
+// chunks of C entries, closed early when the span would pass 65535:
+// emit(chunk, base column, first entry, end) for each; returns their number
+template <typename F>
+int64_t walk_chunks(const std::vector<CsEnt> &E, int64_t C, F &&emit) {
+  int64_t i = 0, cnt = 0;
+  const int64_t ne = (int64_t)E.size();
+  while (i < ne) {
+    const uint32_t c0 = E[(size_t)i].col;
+    int64_t j = i;
+    while (j < ne && j - i < C && E[(size_t)j].col - c0 <= 65535u) ++j;
+    emit(cnt, c0, i, j);
+    ++cnt;
+    i = j;
+  }
+  return cnt;
+}
+
+// per workgroup: sorted entries, chunks, slots (the dummy slot included)
+struct WgEntries {
+  std::vector<std::vector<CsEnt>> ents;
+  std::vector<int64_t> nchunks;
+  std::vector<int32_t> nslots;
+};
+
+// false when a workgroup's slots pass 65536 or the LDS
+bool sort_entries(const Csr &A, const Shape &S, const ColParts &P, const LongRows &L, const WgMap &W,
+                  WgEntries &WE) {
+  const int64_t G = (int64_t)W.sl.size();
+  WE.ents.resize((size_t)G);
+  WE.nchunks.assign((size_t)G, 0);
+  WE.nslots.assign((size_t)G, 0);
   std::atomic<bool> too_big{false};
-  auto chunk_walk = [&](const std::vector<CsEnt> &E, auto &&emit) {
-    // chunks of C entries, closed early when the span would pass 65535
-    int64_t i = 0, cnt_ = 0;
-    const int64_t ne = (int64_t)E.size();
-    while (i < ne) {
-      const uint32_t c0 = E[(size_t)i].col;
-      int64_t j = i;
-      while (j < ne && j - i < C && E[(size_t)j].col - c0 <= 65535u) ++j;
-      emit(cnt_, c0, i, j);
-      ++cnt_;
-      i = j;
-    }
-    return cnt_;
-  };
   parallel_ranges(G, 4, [&](int64_t b0, int64_t b1, int) {
     for (int64_t b = b0; b < b1; ++b) {
-      const int h = (int)(b % H);
-      const int32_t r0 = wg_rows[(size_t)(2 * b)], r1 = wg_rows[(size_t)(2 * b + 1)];
+      const int h = (int)(b % S.H);
+      const int32_t r0 = W.rows[(size_t)(2 * b)], r1 = W.rows[(size_t)(2 * b + 1)];
       const int32_t nr = r1 - r0;
-      auto &E = ents[(size_t)b];
+      auto &E = WE.ents[(size_t)b];
       for (int32_t r = r0; r < r1; ++r) {
-        if (rp[r + 1] - rp[r] > long_t) continue;
-        for (int32_t k = rp[r]; k < rp[r + 1]; ++k)
-          if (part_of(col[k]) == h) E.push_back({(uint32_t)col[k], (uint32_t)(r - r0), (uint32_t)k});
+        if (A.rp[r + 1] - A.rp[r] > S.long_t) continue;
+        for (int32_t k = A.rp[r]; k < A.rp[r + 1]; ++k)
+          if (P.of(A.col[k]) == h) E.push_back({(uint32_t)A.col[k], (uint32_t)(r - r0), (uint32_t)k});
       }
-      const auto &sl = wg_sl[(size_t)b];
+      const auto &sl = W.sl[(size_t)b];
       for (size_t v = 0; v < sl.size(); ++v)
-        for (uint32_t k : slice_k[(size_t)sl[v]])
-          E.push_back({(uint32_t)col[k], (uint32_t)(nr + (int32_t)v), k});
+        for (uint32_t k : L.slice_k[(size_t)sl[v]])
+          E.push_back({(uint32_t)A.col[k], (uint32_t)(nr + (int32_t)v), k});
       std::sort(E.begin(), E.end());
-      nslots[(size_t)b] = nr + (int32_t)sl.size() + 1;  // + the dummy slot
-      if (nslots[(size_t)b] > 65536 || ((int64_t)nslots[(size_t)b] + 1) * slot_bytes > lds_max) too_big = true;
-      nchunks[(size_t)b] = chunk_walk(E, [](int64_t, uint32_t, int64_t, int64_t) {});
+      const int32_t ns = nr + (int32_t)sl.size() + 1;  // + the dummy slot
+      WE.nslots[(size_t)b] = ns;
+      if (ns > 65536 || ((int64_t)ns + 1) * S.slot_bytes > S.lds_max) too_big = true;
+      WE.nchunks[(size_t)b] = walk_chunks(E, S.C, [](int64_t, uint32_t, int64_t, int64_t) {});
     }
   });
-  if (too_big) return HSPMV_OK;
-  std::vector<int32_t> blk_c((size_t)G + 1, 0), blk_v((size_t)G + 1, 0), vslice;
+  return !too_big;
+}
+
+// blk_c, blk_v, vslice, the chunk total and the LDS of the largest
+// workgroup; false when the chunks pass the kernel's index types
+bool table_ranges(const Shape &S, const WgMap &W, const WgEntries &WE, CsortPlan &P) {
+  const size_t G = W.sl.size();
+  P.blk_c.assign(G + 1, 0);
+  P.blk_v.assign(G + 1, 0);
   int64_t tot_chunks = 0;
   int32_t max_slots_used = 1;
-  for (int64_t b = 0; b < G; ++b) {
-    blk_c[(size_t)b] = (int32_t)tot_chunks;
-    tot_chunks += nchunks[(size_t)b];
-    blk_v[(size_t)b] = (int32_t)vslice.size();
-    for (int32_t sl : wg_sl[(size_t)b]) vslice.push_back(sl);
-    max_slots_used = std::max(max_slots_used, nslots[(size_t)b]);
+  for (size_t b = 0; b < G; ++b) {
+    P.blk_c[b] = (int32_t)tot_chunks;
+    tot_chunks += WE.nchunks[b];
+    P.blk_v[b] = (int32_t)P.vslice.size();
+    for (int32_t sl : W.sl[b]) P.vslice.push_back(sl);
+    max_slots_used = std::max(max_slots_used, WE.nslots[b]);
   }
-  blk_c[(size_t)G] = (int32_t)tot_chunks;
-  blk_v[(size_t)G] = (int32_t)vslice.size();
-  if (tot_chunks * C >= (int64_t)1 << 40 || tot_chunks >= INT32_MAX) return HSPMV_OK;
-  const int64_t tot = tot_chunks * C;
-  std::vector<int32_t> slice_row_of((size_t)n_slices, 0);
-  for (size_t j = 0; j + 1 < lcs.size(); ++j)
-    for (int32_t sl = lcs[j]; sl < lcs[j + 1]; ++sl) slice_row_of[(size_t)sl] = lrow[j];
-  auto slice_row = [&](int32_t sl) -> int64_t { return slice_row_of[(size_t)sl]; };
-  // pass 2: the device arrays
-  std::vector<int32_t> cbase((size_t)std::max<int64_t>(tot_chunks, 1), 0);
-  std::vector<uint32_t> idx;
-  std::vector<uint64_t> rec;
-  std::vector<double> val64;
-  if (dtype == HSPMV_F32)
-    rec.assign((size_t)tot, 0);
-  else {
-    idx.assign((size_t)tot, 0);
-    val64.assign((size_t)tot, 0.0);
+  P.blk_c[G] = (int32_t)tot_chunks;
+  P.blk_v[G] = (int32_t)P.vslice.size();
+  P.chunks = tot_chunks;
+  P.lds_bytes = (int32_t)(S.slot_bytes * max_slots_used);
+  return tot_chunks * S.C < (int64_t)1 << 40 && tot_chunks < INT32_MAX;
+}
+
+// Same-slot lanes in one instruction serialise the LDS atomics: an RCM
+// ordering puts a hub row's entries on contiguous columns, so column order
+// can give one instruction 64 lanes of one row (RCM power-law: a few
+// workgroups with ~100 K serialised lanes set the launch's tail, 204 vs
+// 108 us).  Such chunks are stored sorted by slot instead and flagged (bit
+// 31 of the base): the kernel sums each instruction's runs first (segmented
+// scan).  Is the chunk e[0, ne) one of them?
+bool chunk_segmented(const CsEnt *e, int64_t ne, const Tuning &tn) {
+  if (tn.csort_seg == 0) return false;
+  if (tn.csort_seg == 2) return true;
+  uint32_t sl64[64];
+  int64_t extra = 0;
+  for (int64_t g = 0; g < ne; g += 64) {
+    const int64_t w = std::min<int64_t>(64, ne - g);
+    for (int64_t t = 0; t < w; ++t) sl64[t] = e[g + t].slot;
+    std::sort(sl64, sl64 + w);
+    int run = 1, mx = 1;
+    for (int64_t t = 1; t < w; ++t) {
+      run = sl64[t] == sl64[t - 1] ? run + 1 : 1;
+      mx = std::max(mx, run);
+    }
+    extra += mx - 1;
   }
-  std::atomic<int64_t> n_seg{0};  // chunks stored slot-sorted (segmented)
-  // diagnostic builds (Tuning.csort_trace): per workgroup {rows, slices,
-  // chunks, entries, gather quad-sectors, gather sectors, segmented chunks,
-  // 0} -- the cost terms the per-workgroup timelines are compared with
-  constexpr int kWgStats = 8;
+  return extra > (tn.csort_seg_extra > 0 ? tn.csort_seg_extra : kCsortSegExtra);
+}
+
+// The segmented order of the chunk e[0, ne) into out: the crowded rows (>=
+// kCsortSegHeavy entries in this chunk; `all`: every row) first,
+// slot-sorted, in column order within each: their runs are contiguous
+// columns (coalesced gathers); the other entries after them, still in
+// column order.
+void segmented_order(const CsEnt *e, int64_t ne, bool all, std::vector<CsEnt> &out) {
+  std::vector<uint32_t> slots((size_t)ne), heavy;
+  for (int64_t t = 0; t < ne; ++t) slots[(size_t)t] = e[t].slot;
+  std::sort(slots.begin(), slots.end());
+  for (size_t t = 0; t < slots.size();) {
+    size_t end = t;
+    while (end < slots.size() && slots[end] == slots[t]) ++end;
+    if ((int64_t)(end - t) >= kCsortSegHeavy || all) heavy.push_back(slots[t]);
+    t = end;
+  }
+  auto is_heavy = [&](uint32_t sl) { return std::binary_search(heavy.begin(), heavy.end(), sl); };
+  out.clear();
+  for (int64_t t = 0; t < ne; ++t)
+    if (is_heavy(e[t].slot)) out.push_back(e[t]);
+  std::stable_sort(out.begin(), out.end(), [](const CsEnt &a, const CsEnt &b) { return a.slot < b.slot; });
+  for (int64_t t = 0; t < ne; ++t)
+    if (!is_heavy(e[t].slot)) out.push_back(e[t]);
+}
+
+// entry q of a chunk (lane q % 64, u = q / 64) is stored at q, or, for
+// 16-byte loads, interleaved so that one load brings the lane entries u,
+// u+1 (fp32 records, fp64 values: per = 2) or u..u+3 (fp64 indices: per = 4)
+inline int64_t at(bool wide, int64_t q, int per) {
+  if (!wide) return q;
+  const int64_t u = q / 64, lane = q % 64;
+  return (u / per) * (64 * per) + lane * per + (u % per);
+}
+
+// the gather cost terms of one chunk (w[4], w[5] of its workgroup's kWgStats)
+void gather_stats(const CsEnt *src, int64_t ne, uint32_t c0, int64_t C, int sec_shift, int64_t *w) {
+  for (int64_t g = 0; g < C; g += 64) {  // one gather instruction
+    uint32_t sec[64];
+    for (int64_t q = 0; q < 64; ++q) sec[q] = (g + q < ne ? src[g + q].col : c0) >> sec_shift;
+    for (int64_t q = 0; q < 64; q += 4) {  // the L1 serves each quad on its own
+      int d = 1;
+      for (int t = 1; t < 4; ++t) {
+        bool seen = false;
+        for (int t2 = 0; t2 < t; ++t2) seen |= sec[q + t] == sec[q + t2];
+        d += seen ? 0 : 1;
+      }
+      w[4] += d;
+    }
+    std::sort(sec, sec + 64);
+    w[5] += (int64_t)(std::unique(sec, sec + 64) - sec);
+  }
+}
+
+// the slots of one workgroup: its rows, then its slices, then the dummy
+struct WgSlots {
+  int32_t r0, nr;
+  const int32_t *sl, *slice_row;
+  uint32_t dummy;
+  int64_t row_of(uint32_t slot) const {  // source row of a slot (fixed-point scale)
+    return (int32_t)slot < nr ? (int64_t)r0 + slot : slice_row[sl[slot - nr]];
+  }
+};
+
+// the ne entries src of chunk ch, based at column c0, into the entry stream
+void store_chunk(int64_t ch, uint32_t c0, const CsEnt *src, int64_t ne, const Shape &S, const WgSlots &ws,
+                 const Values &V, CsortPlan &P) {
+  const bool f32 = P.dtype == HSPMV_F32;
+  for (int64_t q = 0; q < S.C; ++q) {  // lanes >= ne: padding (gathers x[base])
+    uint32_t ix = ws.dummy << 16;      // padding: 0 * x[base] into the dummy slot
+    if (q < ne) ix = (src[q].slot << 16) | (src[q].col - c0);
+    if (f32) {
+      const uint32_t vb = q < ne ? V.f32(src[q].k, ws.row_of(src[q].slot)) : 0;
+      P.rec[(size_t)(ch * S.C + at(S.wide, q, 2))] = ((uint64_t)vb << 32) | ix;
+    } else {
+      if (q < ne) P.val64[(size_t)(ch * S.C + at(S.wide, q, 2))] = V.f64(src[q].k, ws.row_of(src[q].slot));
+      P.idx[(size_t)(ch * S.C + at(S.wide, q, 4))] = ix;
+    }
+  }
+}
+
+// Chunk encoding: cbase and the entry stream of every workgroup (blk_c and
+// the chunk total are set), the segmented-chunk count and, when asked, the
+// workgroups' statistics.
+// Releases each workgroup's sorted entries as soon as they are stored.
+void encode_chunks(const Shape &S, const Tuning &tn, const LongRows &L, const WgMap &W, const Values &V,
+                   WgEntries &WE, CsortPlan &P) {
+  const int64_t G = (int64_t)W.sl.size(), tot = P.chunks * S.C;
   const bool stats = tn.csort_trace == 1;
-  std::vector<int64_t> wst(stats ? (size_t)(kWgStats * G) : 0, 0);
-  const int sec_shift = dtype == HSPMV_F32 ? 3 : 2;  // x entries per 32-byte sector: 8 / 4
+  P.cbase.assign((size_t)std::max<int64_t>(P.chunks, 1), 0);
+  if (P.dtype == HSPMV_F32)
+    P.rec.assign((size_t)tot, 0);
+  else {
+    P.idx.assign((size_t)tot, 0);
+    P.val64.assign((size_t)tot, 0.0);
+  }
+  if (stats) P.wg_stats.assign((size_t)(kWgStats * G), 0);
+  const int sec_shift = P.dtype == HSPMV_F32 ? 3 : 2;  // x entries per 32-byte sector: 8 / 4
+  std::atomic<int64_t> n_seg{0};  // chunks stored slot-sorted (segmented)
   parallel_ranges(G, 4, [&](int64_t b0, int64_t b1, int) {
+    std::vector<CsEnt> tmp;
     for (int64_t b = b0; b < b1; ++b) {
-      auto &E = ents[(size_t)b];
-      const uint32_t dummy = (uint32_t)(nslots[(size_t)b] - 1);
-      const int32_t br0 = wg_rows[(size_t)(2 * b)], bnr = wg_rows[(size_t)(2 * b + 1)] - br0;
-      const auto &bsl = wg_sl[(size_t)b];
-      auto row_of = [&](uint32_t slot) -> int64_t {  // source row of a slot (fixed-point scale)
-        return (int32_t)slot < bnr ? (int64_t)br0 + slot : slice_row(bsl[slot - bnr]);
-      };
-      const int64_t cfirst = blk_c[(size_t)b];
-      // entry q of a chunk (lane q % 64, u = q / 64) is stored at q, or,
-      // for 16-byte loads, interleaved so that one load brings the lane
-      // entries u, u+1 (fp32 records, fp64 values) or u..u+3 (fp64 indices)
-      auto at = [&](int64_t q, int per) -> int64_t {
-        if (!wide) return q;
-        const int64_t u = q / 64, lane = q % 64;
-        return (u / per) * (64 * per) + lane * per + (u % per);
-      };
-      std::vector<CsEnt> tmp;
-      uint32_t sl64[64];
-      chunk_walk(E, [&](int64_t ci, uint32_t c0, int64_t i, int64_t j) {
-        const int64_t ch = cfirst + ci;
-        // Same-slot lanes in one instruction serialise the LDS atomics:
-        // an RCM ordering puts a hub row's entries on contiguous columns,
-        // so column order can give one instruction 64 lanes of one row
-        // (RCM power-law: a few workgroups with ~100 K serialised lanes
-        // set the launch's tail, 204 vs 108 us).  Such chunks are stored
-        // sorted by slot instead and flagged (bit 31 of the base): the
-        // kernel sums each instruction's runs first (segmented scan).
+      auto &E = WE.ents[(size_t)b];
+      const int32_t r0 = W.rows[(size_t)(2 * b)];
+      const WgSlots ws{r0, W.rows[(size_t)(2 * b + 1)] - r0, W.sl[(size_t)b].data(), L.slice_row.data(),
+                       (uint32_t)(WE.nslots[(size_t)b] - 1)};
+      int64_t *w = stats ? P.wg_stats.data() + kWgStats * b : nullptr;
+      if (w) {
+        w[0] = ws.nr;
+        w[1] = (int64_t)W.sl[(size_t)b].size();
+      }
+      walk_chunks(E, S.C, [&](int64_t ci, uint32_t c0, int64_t i, int64_t j) {
+        const int64_t ch = P.blk_c[(size_t)b] + ci, ne = j - i;
         const CsEnt *src = E.data() + i;
-        bool seg = false;
-        if (tn.csort_seg != 0) {
-          int64_t extra = 0;
-          for (int64_t g = i; g < j; g += 64) {
-            const int64_t e = std::min(j, g + 64);
-            for (int64_t t = g; t < e; ++t) sl64[t - g] = E[(size_t)t].slot;
-            std::sort(sl64, sl64 + (e - g));
-            int run = 1, mx = 1;
-            for (int64_t t = 1; t < e - g; ++t) {
-              run = sl64[t] == sl64[t - 1] ? run + 1 : 1;
-              mx = std::max(mx, run);
-            }
-            extra += mx - 1;
-          }
-          const int64_t lim = tn.csort_seg_extra > 0 ? tn.csort_seg_extra : kCsortSegExtra;
-          if (extra > lim || tn.csort_seg == 2) {
-            // the crowded rows (>= kCsortSegHeavy entries in this chunk)
-            // first, slot-sorted, in column order within each: their runs
-            // are contiguous columns (coalesced gathers); the other
-            // entries after them, still in column order
-            std::vector<std::pair<uint32_t, int32_t>> cnt_s;
-            cnt_s.reserve((size_t)(j - i));
-            for (int64_t t = i; t < j; ++t) cnt_s.push_back({E[(size_t)t].slot, 0});
-            std::sort(cnt_s.begin(), cnt_s.end());
-            std::vector<uint32_t> heavy;
-            for (size_t t = 0; t < cnt_s.size();) {
-              size_t e = t;
-              while (e < cnt_s.size() && cnt_s[e].first == cnt_s[t].first) ++e;
-              if ((int64_t)(e - t) >= kCsortSegHeavy || tn.csort_seg == 2) heavy.push_back(cnt_s[t].first);
-              t = e;
-            }
-            auto is_heavy = [&](uint32_t sl) { return std::binary_search(heavy.begin(), heavy.end(), sl); };
-            tmp.clear();
-            for (int64_t t = i; t < j; ++t)
-              if (is_heavy(E[(size_t)t].slot)) tmp.push_back(E[(size_t)t]);
-            std::stable_sort(tmp.begin(), tmp.end(), [](const CsEnt &a, const CsEnt &b) { return a.slot < b.slot; });
-            for (int64_t t = i; t < j; ++t)
-              if (!is_heavy(E[(size_t)t].slot)) tmp.push_back(E[(size_t)t]);
-            src = tmp.data();
-            seg = true;
-            n_seg.fetch_add(1, std::memory_order_relaxed);
-          }
+        const bool seg = chunk_segmented(src, ne, tn);
+        if (seg) {
+          segmented_order(src, ne, tn.csort_seg == 2, tmp);
+          src = tmp.data();
+          n_seg.fetch_add(1, std::memory_order_relaxed);
         }
-        cbase[(size_t)ch] = (int32_t)(c0 | (seg ? 0x80000000u : 0u));
-        const int64_t ne = j - i;  // lanes >= ne: padding (gathers x[base])
-        if (stats) {
-          int64_t *w = wst.data() + kWgStats * b;
+        P.cbase[(size_t)ch] = (int32_t)(c0 | (seg ? 0x80000000u : 0u));
+        if (w) {
           w[2] += 1;
-          w[3] += j - i;
+          w[3] += ne;
           w[6] += seg ? 1 : 0;
-          for (int64_t g = 0; g < C; g += 64) {  // one gather instruction
-            uint32_t sec[64];
-            for (int64_t q = 0; q < 64; ++q)
-              sec[q] = (g + q < ne ? src[g + q].col : c0) >> sec_shift;
-            for (int64_t q = 0; q < 64; q += 4) {  // the L1 serves each quad on its own
-              int d = 1;
-              for (int t = 1; t < 4; ++t) {
-                bool seen = false;
-                for (int t2 = 0; t2 < t; ++t2) seen |= sec[q + t] == sec[q + t2];
-                d += seen ? 0 : 1;
-              }
-              w[4] += d;
-            }
-            std::sort(sec, sec + 64);
-            w[5] += (int64_t)(std::unique(sec, sec + 64) - sec);
-          }
+          gather_stats(src, ne, c0, S.C, sec_shift, w);
         }
-        for (int64_t q = 0; q < C; ++q) {
-          const int64_t o = ch * C + at(q, dtype == HSPMV_F32 ? 2 : 4);
-          const int64_t ov = ch * C + at(q, 2);
-          uint32_t ix = dummy << 16;  // padding: 0 * x[base] into the dummy slot
-          if (dtype == HSPMV_F32) {
-            uint32_t vb = 0;
-            if (q < ne) {
-              const CsEnt &e = src[q];
-              ix = (e.slot << 16) | (e.col - c0);
-              vb = value_f32(e.k, row_of(e.slot));
-            }
-            rec[(size_t)o] = ((uint64_t)vb << 32) | ix;
-          } else {
-            if (q < ne) {
-              const CsEnt &e = src[q];
-              ix = (e.slot << 16) | (e.col - c0);
-              val64[(size_t)ov] = value_f64(e.k, row_of(e.slot));
-            }
-            idx[(size_t)o] = ix;
-          }
-        }
+        store_chunk(ch, c0, src, ne, S, ws, V, P);
       });
       std::vector<CsEnt>().swap(E);
     }
   });
-  std::vector<uint32_t> mask;
-  if (!lrow.empty()) {
-    mask.assign((size_t)((m + 31) / 32), 0u);
-    for (int32_t r : lrow) mask[(size_t)r >> 5] |= 1u << (r & 31);
+  P.seg_chunks = n_seg.load();
+}
+
+// The launch's flags, the device-only arrays' sizes and the bytes moved
+// (the plan's shape -- m, n, dtype, H, n_wg, n_long, fixed, chunks -- is set).
+void plan_scalars(const Shape &S, const Tuning &tn, int64_t n_slices, CsortPlan &P) {
+  const bool f32 = P.dtype == HSPMV_F32;
+  P.u = S.U;
+  P.direct = P.H == 1 && P.n_long == 0;
+  P.nontemporal = true;  // the entry stream is read once; keep x in the caches
+  if (tn.csort_nt >= 0) P.nontemporal = tn.csort_nt != 0;  // A/B knobs
+  P.prefetch = S.wide && f32;  // see `wide` (csort_shape)
+  if (tn.csort_pf >= 0) P.prefetch = tn.csort_pf != 0;
+  P.slot32 = S.slot32;
+  P.wide = S.wide;
+  // Row partials: fp32 for fp32 data (part32, the default since r06; the
+  // LDS slots stay fp64 and the finishing pass adds in fp64): half of C5's
+  // 64 MB of partial traffic, C5 98.2 -> 91.9 us, c5r 99.2 -> 94.5 (t_min,
+  // one process, profiles/r05q1/ab_part32.jsonl).  y then rounds twice on
+  // rows with entries in both column parts (the part's sum, then y):
+  // |y - y64| <= 2^-24 (sum_h |p_h| + |y64|), inside omp_spmv's own fp32
+  // error (len + 2) 2^-23 sum|a x| (tests/test_gpu_parity.py).  Tuning
+  // csort_part32 = 0 keeps fp64 partials (A/B).
+  P.part32 = f32 && !S.slot32 && tn.csort_part32 != 0;
+  // waves claim chunks from the workgroup's LDS queue: one process, 7
+  // rounds (profiles/r05c/ab_csort_dyn.jsonl): C5 106.9 -> 101.9 us median,
+  // c5r 107.3 -> 104.9, fp64 C5 flat (175.7 -> 174.7)
+  P.dyn = tn.csort_dyn != 0;
+  P.fin_rows = tn.csort_fin_rows;
+  // (An in-launch combine -- write-through partials, an arrival counter per
+  // row block, the last arriver adding the parts -- measured slower than
+  // the finishing launch: C5 114.8 vs 107.3 us, profiles/r02s_*.)
+  if (!P.direct) {
+    P.part_bytes = (P.part32 ? 4 : (size_t)S.slot_bytes) * (size_t)P.H * (size_t)P.m;
+    P.spart_bytes = (size_t)S.slot_bytes * (size_t)std::max<int64_t>(n_slices, 1);
   }
+  if (P.fixed) {  // the x-exponent pre-pass: one block per 8192 entries of x, at most kCsortXexpBlocks
+    P.n_xexp = (int32_t)std::min<int64_t>(kCsortXexpBlocks,
+                                          std::max<int64_t>(1, (P.n + kCsortXexpChunk - 1) / kCsortXexpChunk));
+    P.xexp_part_bytes = 4 * (size_t)P.n_xexp;
+  }
+  if (tn.csort_trace == 1) P.trace_bytes = 8 * kCsortTraceSlots * (size_t)P.n_wg;
+  // bytes moved: the entry stream + chunk bases + the partial sums written
+  // and read back + y (upload_csort adds x: the shard's distinct columns)
+  const double sv = (double)dtype_size(P.dtype), tot = (double)P.chunks * (double)S.C;
+  const double part_traffic =
+      P.direct ? 0.0 : 2.0 * ((double)P.part_bytes + (double)S.slot_bytes * (double)n_slices);
+  // (fixed-point: + the x exponent's read of x and the row scales)
+  const double fix_traffic = P.fixed ? (double)P.n * sv + 2.0 * (double)P.H * (double)P.m : 0.0;
+  P.format_bytes = tot * (4.0 + sv) + 4.0 * (double)P.chunks + part_traffic + sv * (double)P.m + fix_traffic;
+}
+
+}  // namespace
+
+bool plan_csort(const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n, int dtype,
+                unsigned flags, const Tuning &tn, const CsortLimits &lim, CsortPlan &P) {
+  if (m == 0 || n == 0 || !val) return false;
+  P = CsortPlan();
+  P.m = m;
+  P.n = n;
+  P.dtype = dtype;
+  const Csr A{rp, col, val, m, n, dtype};
+  const Shape S = csort_shape(A, flags, tn, lim);
+  const ColParts parts = column_parts(A, S, tn);
+  const LongRows L = long_rows(A, S, parts);
+  P.fixed = tn.deterministic == 2 && !S.slot32 && row_scales(A, S.long_t, L, P.rexp, P.sexp);
+  const int64_t reserve = L.n_slices() / S.nb0 + 2;
+  const int64_t row_cap = S.max_slots - 1 - reserve;
+  if (row_cap < 64) return false;  // too many slices for the LDS: not this path
+  const std::vector<std::vector<int32_t>> brh = row_blocks(A, S, parts, tn, row_cap);
+  int64_t NB = 0;
+  for (const auto &b : brh) NB = std::max<int64_t>(NB, (int64_t)b.size() - 1);
+  const int64_t G = NB * S.H;
+  if (G >= INT32_MAX) return false;
+  P.n_wg = (int32_t)G;
+  P.H = S.H;
+  P.row_blocks = (int32_t)NB;
+  const WgMap W = deal_workgroups(brh, G, m, L);
+  WgEntries WE;
+  if (!sort_entries(A, S, parts, L, W, WE)) return false;
+  if (!table_ranges(S, W, WE, P)) return false;
+  encode_chunks(S, tn, L, W, Values{val, P.fixed ? P.rexp.data() : nullptr}, WE, P);
+  P.blk_r = W.rows;
+  P.n_long = (int32_t)L.row.size();
+  if (P.n_long) {
+    P.long_mask.assign((size_t)((m + 31) / 32), 0u);
+    for (int32_t r : L.row) P.long_mask[(size_t)r >> 5] |= 1u << (r & 31);
+    P.long_row = L.row;
+    P.long_cs = L.cs;
+  }
+  for (int h = 0; h < S.H; ++h) P.part_begin[h] = parts.pb[(size_t)h];
+  plan_scalars(S, tn, L.n_slices(), P);
+  return true;
+}
+
+int upload_csort(Shard &s, const CsortPlan &P) {
   int rc;
   // the tables go straight into the launch description (s.dev owns them)
   DevCsort &c = s.csort;
@@ -542,89 +726,64 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
     if (h.empty()) return s.dev.alloc(d, sizeof(E));  // one element's room, as for a size of 1
     return s.dev.upload(d, h.data(), sizeof(E) * h.size());
   };
-  if ((rc = up(&c.blk_c, blk_c)) || (rc = up(&c.blk_r, wg_rows)) || (rc = up(&c.blk_v, blk_v)) ||
-      (rc = up(&c.vslice, vslice)) || (rc = up(&c.cbase, cbase)))
+  if ((rc = up(&c.blk_c, P.blk_c)) || (rc = up(&c.blk_r, P.blk_r)) || (rc = up(&c.blk_v, P.blk_v)) ||
+      (rc = up(&c.vslice, P.vslice)) || (rc = up(&c.cbase, P.cbase)))
     return rc;
-  if (dtype == HSPMV_F32) {
-    if ((rc = up(&c.ent, rec))) return rc;
+  if (P.dtype == HSPMV_F32) {
+    if ((rc = up(&c.ent, P.rec))) return rc;
   } else {
-    if ((rc = up(&c.ent, idx)) || (rc = up(&c.val, val64))) return rc;
+    if ((rc = up(&c.ent, P.idx)) || (rc = up(&c.val, P.val64))) return rc;
   }
-  const bool direct = H == 1 && lrow.empty();
-  // Row partials: fp32 for fp32 data (part32, the default since r06; the
-  // LDS slots stay fp64 and the finishing pass adds in fp64): half of C5's
-  // 64 MB of partial traffic, C5 98.2 -> 91.9 us, c5r 99.2 -> 94.5 (t_min,
-  // one process, profiles/r05q1/ab_part32.jsonl).  y then rounds twice on
-  // rows with entries in both column parts (the part's sum, then y):
-  // |y - y64| <= 2^-24 (sum_h |p_h| + |y64|), inside omp_spmv's own fp32
-  // error (len + 2) 2^-23 sum|a x| (tests/test_gpu_parity.py).  Tuning
-  // csort_part32 = 0 keeps fp64 partials (A/B).
-  const bool part32 = dtype == HSPMV_F32 && !slot32 && tn.csort_part32 != 0;
-  const int64_t part_bytes = part32 ? 4 : slot_bytes;
-  if (!direct) {
-    if ((rc = s.dev.alloc(&c.part, part_bytes * (size_t)H * (size_t)m))) return rc;
-    if ((rc = s.dev.alloc(&c.spart, slot_bytes * (size_t)std::max<int64_t>(n_slices, 1)))) return rc;
-  }
-  if (!lrow.empty()) {
-    if ((rc = up(&c.long_mask, mask)) || (rc = up(&c.long_row, lrow)) || (rc = up(&c.long_cs, lcs)))
-      return rc;
-  }
-  int32_t n_xexp = 0;
-  if (fixed) {  // the x-exponent pre-pass: one block per 8192 entries of x, at most kCsortXexpBlocks
-    if ((rc = up(&c.rexp, rexp)) || (rc = up(&c.sexp, sexp))) return rc;
-    n_xexp = (int32_t)std::min<int64_t>(kCsortXexpBlocks,
-                                        std::max<int64_t>(1, (n + kCsortXexpChunk - 1) / kCsortXexpChunk));
-    if ((rc = s.dev.alloc(&c.xexp_part, 4 * (size_t)n_xexp))) return rc;
-  }
-  // (An in-launch combine -- write-through partials, an arrival counter per
-  // row block, the last arriver adding the parts -- measured slower than
-  // the finishing launch: C5 114.8 vs 107.3 us, profiles/r02s_*.)
-  c.n_wg = (int32_t)G;
-  c.H = H;
-  c.u = U;
-  c.direct = direct ? 1 : 0;
-  c.n_long = (int32_t)lrow.size();
-  c.nontemporal = true;  // the entry stream is read once; keep x in the caches
-  if (tn.csort_nt >= 0) c.nontemporal = tn.csort_nt != 0;  // A/B knobs
-  c.prefetch = wide && dtype == HSPMV_F32;  // see `wide` above
-  if (tn.csort_pf >= 0) c.prefetch = tn.csort_pf != 0;
-  c.slot32 = slot32;
-  c.part32 = part32;
-  c.wide = wide;
-  c.fin_rows = tn.csort_fin_rows;
-  c.fixed = fixed;
-  c.n_xexp = n_xexp;
-  c.n_x = n;
-  // waves claim chunks from the workgroup's LDS queue: one process, 7
-  // rounds (profiles/r05c/ab_csort_dyn.jsonl): C5 106.9 -> 101.9 us median,
-  // c5r 107.3 -> 104.9, fp64 C5 flat (175.7 -> 174.7)
-  c.dyn = tn.csort_dyn != 0;
-  c.m = m;
-  c.lds_bytes = (int32_t)(slot_bytes * max_slots_used);
-  c.row_blocks = (int32_t)NB;
-  s.csort_seg_chunks = n_seg.load();
-  if (stats) {
-    for (int64_t b = 0; b < G; ++b) {
-      wst[(size_t)(kWgStats * b)] = wg_rows[(size_t)(2 * b + 1)] - wg_rows[(size_t)(2 * b)];
-      wst[(size_t)(kWgStats * b + 1)] = (int64_t)wg_sl[(size_t)b].size();
-    }
-    s.csort_wg_stats.swap(wst);
-  }
-  s.csort_chunks = tot_chunks;
-  for (int h = 0; h < 4; ++h) s.csort_part_begin[h] = h < H ? pb[(size_t)h] : 0;
-  if (tn.csort_trace == 1 && (rc = s.dev.alloc(&c.trace, 8 * kCsortTraceSlots * (size_t)G))) return rc;
-  // bytes moved: the entry stream + chunk bases + x (distinct columns) + the
-  // partial sums written and read back + y
-  const double xb = (double)s.x_entries * (double)sv;
-  const double part_traffic =
-      direct ? 0.0
-             : 2.0 * ((double)part_bytes * (double)H * (double)m + (double)slot_bytes * (double)n_slices);
-  // (fixed-point: + the x exponent's read of x and the row scales)
-  const double fix_traffic = fixed ? (double)n * (double)sv + 2.0 * (double)H * (double)m : 0.0;
-  s.csort_format_bytes = (double)tot * (double)(4 + sv) + 4.0 * (double)tot_chunks + xb + part_traffic +
-                         (double)sv * (double)m + fix_traffic;
+  if (!P.direct && ((rc = s.dev.alloc(&c.part, P.part_bytes)) || (rc = s.dev.alloc(&c.spart, P.spart_bytes))))
+    return rc;
+  if (P.n_long && ((rc = up(&c.long_mask, P.long_mask)) || (rc = up(&c.long_row, P.long_row)) ||
+                   (rc = up(&c.long_cs, P.long_cs))))
+    return rc;
+  if (P.fixed && ((rc = up(&c.rexp, P.rexp)) || (rc = up(&c.sexp, P.sexp)) ||
+                  (rc = s.dev.alloc(&c.xexp_part, P.xexp_part_bytes))))
+    return rc;
+  if (P.trace_bytes && (rc = s.dev.alloc(&c.trace, P.trace_bytes))) return rc;
+  c.n_wg = P.n_wg;
+  c.H = P.H;
+  c.u = P.u;
+  c.direct = P.direct ? 1 : 0;
+  c.n_long = P.n_long;
+  c.nontemporal = P.nontemporal;
+  c.prefetch = P.prefetch;
+  c.slot32 = P.slot32;
+  c.part32 = P.part32;
+  c.wide = P.wide;
+  c.dyn = P.dyn;
+  c.fixed = P.fixed;
+  c.fin_rows = P.fin_rows;
+  c.n_xexp = P.n_xexp;
+  c.n_x = P.n;
+  c.m = P.m;
+  c.lds_bytes = P.lds_bytes;
+  c.row_blocks = P.row_blocks;
+  s.csort_chunks = P.chunks;
+  s.csort_seg_chunks = P.seg_chunks;
+  s.csort_wg_stats = P.wg_stats;
+  for (int h = 0; h < 4; ++h) s.csort_part_begin[h] = P.part_begin[h];
+  s.csort_format_bytes = P.format_bytes + (double)s.x_entries * (double)dtype_size(P.dtype);
   s.A.has_csort = true;
   return HSPMV_OK;
+}
+
+int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n,
+                int dtype, unsigned flags) {
+  CsortLimits lim{0, 0};
+  if (hipDeviceGetAttribute(&lim.cus, hipDeviceAttributeMultiprocessorCount, s.dev.device) != hipSuccess ||
+      lim.cus <= 0)
+    lim.cus = 256;
+  int lds_max = 0;  // the row slots must fit one workgroup's LDS on THIS device
+  if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, s.dev.device) != hipSuccess ||
+      lds_max <= 0)
+    return HSPMV_OK;
+  lim.lds_bytes = std::min(lds_max, kCsortMaxLds) - kCsortStaticLds;
+  CsortPlan P;
+  if (!plan_csort(rp, col, val, m, n, dtype, flags, s.tune, lim, P)) return HSPMV_OK;
+  return upload_csort(s, P);
 }
 
 }  // namespace hspmv

@@ -203,6 +203,9 @@ inline int32_t flag_groups(unsigned flags) {
 // blk_v[b+1]).  Built by build_csort (hspmv_csort_build.cpp).
 constexpr int kCsortThreads = 1024;
 constexpr int kCsortMaxLds = 160 * 1024;
+// the kernel's static LDS (its chunk-queue head, 16 B with alignment) comes
+// out of the same budget as the row slots (build_csort)
+constexpr int kCsortStaticLds = 16;
 // Diagnostic trace of a csort launch (DevCsort.trace, HSPMV_CSORT_TRACE=1):
 // per workgroup kCsortTraceSlots u64 = {start, end, XCC_ID | HW_ID << 32,
 // after the slot-zeroing barrier, then per wave: its end (after its last

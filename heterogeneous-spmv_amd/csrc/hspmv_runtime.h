@@ -12,7 +12,8 @@
 //   hspmv_xdict.cpp        block x dictionaries (+ hspmv_xdict_plan), the
 //                          plan entry points' shared preamble (plan_shape)
 //   hspmv_slices.cpp       row slices of dictionary handles (+ hspmv_slices_plan)
-//   hspmv_csort_build.cpp  column-sorted row blocks (csort.hip's tables)
+//   hspmv_csort_build.cpp  column-sorted row blocks (csort.hip's tables):
+//                          plan_csort (host only), upload_csort, build_csort
 //   hspmv_update.cpp       new values for a planned shard (hspmv_update_values)
 //   hspmv_multi.cpp        the row-range partition over devices, RCCL
 //   hspmv_api.cpp          the C ABI entry points
@@ -319,6 +320,47 @@ int upload_slices(Shard &s, const SlicePlan &P);
 void drop_slices(Shard &s);
 
 // ---- hspmv_csort_build.cpp
+// What the device says: its CUs, and the LDS bytes a workgroup's row slots may take.
+struct CsortLimits {
+  int cus;
+  int lds_bytes;
+};
+// The column-sorted tables of one shard on the host: what upload_csort puts on
+// the device or into the shard's report, and nothing else (DevCsort,
+// hspmv_internal.h, says what the tables and the launch scalars mean).
+struct CsortPlan {
+  int64_t m = 0, n = 0;
+  int dtype = HSPMV_F64;
+  std::vector<int32_t> blk_c, blk_r, blk_v, vslice, cbase;
+  std::vector<uint64_t> rec;   // the entry stream, fp32: {idx, val} records
+  std::vector<uint32_t> idx;   // ... fp64: indices
+  std::vector<double> val64;   // ... and values
+  std::vector<uint32_t> long_mask;
+  std::vector<int32_t> long_row, long_cs;  // (empty without long rows)
+  std::vector<int16_t> rexp, sexp;         // (empty unless fixed)
+  int32_t n_wg = 0, H = 1, u = 16, n_long = 0;
+  bool direct = false, nontemporal = true, prefetch = false, slot32 = false, part32 = false, wide = false,
+       dyn = false, fixed = false;
+  int32_t fin_rows = 0, lds_bytes = 0, row_blocks = 0, n_xexp = 0;
+  // bytes of the device-only arrays (0: none): part, spart, xexp_part, trace
+  size_t part_bytes = 0, spart_bytes = 0, xexp_part_bytes = 0, trace_bytes = 0;
+  int64_t chunks = 0, seg_chunks = 0;  // chunks, and those stored slot-sorted
+  int64_t part_begin[4] = {0, 0, 0, 0};  // first column of each column part
+  std::vector<int64_t> wg_stats;  // Tuning.csort_trace: 8 cost terms per workgroup
+  double format_bytes = 0.0;      // bytes one SpMV moves, x apart (upload_csort adds the shard's)
+};
+// The host-only planner (no HIP call, no Shard): false when the matrix does
+// not take this path (an empty shape, no values, too many long-row slices or
+// rows for the LDS slots, chunk counts past the index types), P then
+// unspecified.  tools/csort_plan_check.cpp decodes its tables back into the
+// matrix (make asan-csort; tests/test_csort_plan.py).
+bool plan_csort(const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n, int dtype,
+                unsigned flags, const Tuning &tune, const CsortLimits &lim, CsortPlan &P);
+// Uploads and allocations only: fills s.csort, the shard's csort_* report
+// fields (format bytes with the x term of s.x_entries) and s.A.has_csort.
+int upload_csort(Shard &s, const CsortPlan &P);
+// The device's two limits, plan_csort, upload_csort; HSPMV_OK without tables
+// (s.A.has_csort stays false) when the planner declines.
 int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
                 int64_t n, int dtype, unsigned flags);
 

@@ -30,6 +30,7 @@ import hspmv  # noqa: E402
 from hspmv import _lib, gen  # noqa: E402
 from hspmv.api import _KERNELS, dtype_code  # noqa: E402
 from ab import load  # noqa: E402
+from test_csort import _hub_rows as csort_hub_rows, _long_rows as csort_long_rows  # noqa: E402
 from test_serial import long_rows  # noqa: E402
 from test_slice_pos12 import OFF, ON, block_run, ragged_all_widths  # noqa: E402
 from test_spmm import long_matrix  # noqa: E402
@@ -125,6 +126,16 @@ def families():
     yield "x_slabs3", lambda L: S(L, st21, kernel="stream", options={"x_slabs": 3})
     yield "csort", lambda L: S(L, pl, kernel="csort")
     yield "csort_reproducible", lambda L: S(L, pl, kernel="csort", options={"deterministic": 2})
+    # every branch of the csort tables: fp32, one and four column parts,
+    # sliced long rows, segmented hub-row chunks; each also reproducible
+    # (fixed-point: y byte for byte)
+    csort_mats = [("f32", pl.astype(np.float32), {}), ("parts1", pl, {"csort_parts": 1}),
+                  ("parts4", pl, {"csort_parts": 4}), ("long_rows", csort_long_rows(), {}),
+                  ("hub_rows", csort_hub_rows(), {})]
+    for tag, A, o in csort_mats:
+        yield f"csort_{tag}", lambda L, A=A, o=o: S(L, A, kernel="csort", options=o)
+        yield (f"csort_{tag}_reproducible",
+               lambda L, A=A, o=o: S(L, A, kernel="csort", options={**o, "deterministic": 2}))
     yield "long_rows", lambda L: S(L, lr)
     yield "long_rows_serial", lambda L: S(L, lr, options={"deterministic": 3})
     yield "devices_0_0", lambda L: S(L, lap, devices=[0, 0])
