@@ -45,7 +45,8 @@
 //                       column ones); flops = 2 nnz K; prints "Rhs: K"; the
 //                       check runs per column; --dump-y writes the row-major
 //                       m x K array.  One GPU, the automatic kernel only.
-//   --update-values N   after the timed loop and its report: N rounds of
+//   --update-values N   the handle is created by hspmv_create_updatable; after
+//                       the timed loop and its report: N rounds of
 //                       hspmv_update_values on the planned handle from host
 //                       memory, round k with the file's values times 1 +
 //                       2^-(k+1); prints "UpdateMin:" / "UpdateAvg:" (wall
@@ -365,7 +366,10 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
   opt.deterministic = o.deterministic;
   // vdt: the type of x and y (the values' unless --vector-dtype gives another)
   const int vdt = o.vector_dtype >= 0 ? o.vector_dtype : A.dtype;
-  if (vdt != A.dtype) {
+  if (o.update_values > 0) {  // a handle that takes new values in every plan, the column-sorted one too
+    if (hspmv_create_updatable(&h, &view, mv.n_ssr > 0 ? &mv : nullptr, &opt, vdt) != HSPMV_OK)
+      return die("hspmv_create_updatable");
+  } else if (vdt != A.dtype) {
     if (hspmv_create_mixed(&h, &view, mv.n_ssr > 0 ? &mv : nullptr, &opt, vdt) != HSPMV_OK)
       return die("hspmv_create_mixed");
   } else if (hspmv_create_ex(&h, &view, mv.n_ssr > 0 ? &mv : nullptr, &opt) != HSPMV_OK) {

@@ -158,15 +158,19 @@ int hspmv_create_on_device(hspmv_handle **hp, const hspmv_csr *A, const hspmv_cs
   return create_single(hp, A, maps, device, stream, flags, default_tuning());
 }
 
-int hspmv_create_ex(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps,
-                    const hspmv_options *opt) {
-  clear_error();
-  if (!hp) return set_error(HSPMV_E_INVALID, "NULL handle pointer");
-  *hp = nullptr;
+}  // extern "C"
+
+namespace {
+
+// hspmv_create_ex; updatable: column-sorted tables keep their source indices
+// (hspmv_create_updatable)
+int create_ex(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt,
+              bool updatable) {
   Tuning t;
   int rc;
   if ((rc = tuning_from_options(opt, &t))) return rc;
   tuning_from_env(&t);  // diagnostic builds only
+  t.csort_src = updatable ? 1 : 0;
   const unsigned flags = opt ? opt->flags : 0u;
   if (opt && opt->devices) {
     if (flags & HSPMV_FLAG_DEVICE_PTRS)
@@ -180,16 +184,15 @@ int hspmv_create_ex(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps
   return create_single(hp, A, maps, opt ? opt->device : 0, opt ? opt->stream : nullptr, flags, t);
 }
 
-int hspmv_create_mixed(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps,
-                       const hspmv_options *opt, int vector_dtype) {
-  clear_error();
-  if (!hp) return set_error(HSPMV_E_INVALID, "NULL handle pointer");
-  *hp = nullptr;
+// hspmv_create_mixed (a mixed handle builds no column-sorted tables, so
+// `updatable` matters for equal dtypes only)
+int create_mixed(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps, const hspmv_options *opt,
+                 int vector_dtype, bool updatable) {
   if (!A) return set_error(HSPMV_E_INVALID, "matrix is NULL");
   // every refusal below comes before the first HIP call (no device needed)
   int rc;
   if ((rc = check_dtype_pair(A->dtype, vector_dtype))) return rc;
-  if (vector_dtype == A->dtype) return hspmv_create_ex(hp, A, maps, opt);
+  if (vector_dtype == A->dtype) return create_ex(hp, A, maps, opt, updatable);
   Tuning t;
   if ((rc = tuning_from_options(opt, &t))) return rc;
   tuning_from_env(&t);  // diagnostic builds only
@@ -202,6 +205,34 @@ int hspmv_create_mixed(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_m
                                       "kernel: HSPMV_KERNEL_CSORT / csort = 1 need equal dtypes");
   const int device = opt ? (opt->devices ? opt->devices[0] : opt->device) : 0;
   return create_single(hp, A, maps, device, opt ? opt->stream : nullptr, flags, t, vector_dtype);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hspmv_create_ex(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps,
+                    const hspmv_options *opt) {
+  clear_error();
+  if (!hp) return set_error(HSPMV_E_INVALID, "NULL handle pointer");
+  *hp = nullptr;
+  return create_ex(hp, A, maps, opt, false);
+}
+
+int hspmv_create_mixed(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps,
+                       const hspmv_options *opt, int vector_dtype) {
+  clear_error();
+  if (!hp) return set_error(HSPMV_E_INVALID, "NULL handle pointer");
+  *hp = nullptr;
+  return create_mixed(hp, A, maps, opt, vector_dtype, false);
+}
+
+int hspmv_create_updatable(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *maps,
+                           const hspmv_options *opt, int vector_dtype) {
+  clear_error();
+  if (!hp) return set_error(HSPMV_E_INVALID, "NULL handle pointer");
+  *hp = nullptr;
+  return create_mixed(hp, A, maps, opt, vector_dtype, true);
 }
 
 int hspmv_get_dtypes(hspmv_handle *h, int *value_dtype, int *vector_dtype) {
@@ -289,11 +320,21 @@ int hspmv_update_values(hspmv_handle *h, const void *val, unsigned flags) {
   if (h->nnz == 0) return HSPMV_OK;
   if (!val && !borrowed) return set_error(HSPMV_E_INVALID, "val is NULL");
   const size_t sv = dtype_size(h->val_dtype);
+  if (!on_device)  // (a device source: finite values are the caller's duty, include/hspmv.h)
+    for (const Shard &s : h->shards)
+      if ((rc = update_values_finite(s, (const char *)val + sv * (size_t)s.nnz0))) return rc;
   for (Shard &s : h->shards) {
     const void *v = val ? (const char *)val + sv * (size_t)s.nnz0 : nullptr;
     if ((rc = update_shard_values(s, v, on_device, borrowed))) return rc;
   }
   return HSPMV_OK;
+}
+
+int hspmv_can_update_values(const hspmv_handle *h) {
+  if (!h || h->shards.empty()) return 0;
+  for (const Shard &s : h->shards)
+    if (!shard_can_update(s)) return 0;
+  return 1;
 }
 
 int hspmv_bind_x_device(hspmv_handle *h, const void *x_dev) {

@@ -554,12 +554,15 @@ struct WgSlots {
 };
 
 // the ne entries src of chunk ch, based at column c0, into the entry stream
+// (and, for an updatable handle, their CSR indices into P.src, at the
+// positions of their values)
 void store_chunk(int64_t ch, uint32_t c0, const CsEnt *src, int64_t ne, const Shape &S, const WgSlots &ws,
                  const Values &V, CsortPlan &P) {
   const bool f32 = P.dtype == HSPMV_F32;
   for (int64_t q = 0; q < S.C; ++q) {  // lanes >= ne: padding (gathers x[base])
     uint32_t ix = ws.dummy << 16;      // padding: 0 * x[base] into the dummy slot
     if (q < ne) ix = (src[q].slot << 16) | (src[q].col - c0);
+    if (!P.src.empty()) P.src[(size_t)(ch * S.C + at(S.wide, q, 2))] = q < ne ? src[q].k : kCsortSrcPad;
     if (f32) {
       const uint32_t vb = q < ne ? V.f32(src[q].k, ws.row_of(src[q].slot)) : 0;
       P.rec[(size_t)(ch * S.C + at(S.wide, q, 2))] = ((uint64_t)vb << 32) | ix;
@@ -585,6 +588,7 @@ void encode_chunks(const Shape &S, const Tuning &tn, const LongRows &L, const Wg
     P.idx.assign((size_t)tot, 0);
     P.val64.assign((size_t)tot, 0.0);
   }
+  if (tn.csort_src == 1) P.src.assign((size_t)std::max<int64_t>(tot, 1), kCsortSrcPad);
   if (stats) P.wg_stats.assign((size_t)(kWgStats * G), 0);
   const int sec_shift = P.dtype == HSPMV_F32 ? 3 : 2;  // x entries per 32-byte sector: 8 / 4
   std::atomic<int64_t> n_seg{0};  // chunks stored slot-sorted (segmented)
@@ -684,6 +688,7 @@ bool plan_csort(const int32_t *rp, const int32_t *col, const void *val, int64_t 
   P.dtype = dtype;
   const Csr A{rp, col, val, m, n, dtype};
   const Shape S = csort_shape(A, flags, tn, lim);
+  P.long_t = S.long_t;
   const ColParts parts = column_parts(A, S, tn);
   const LongRows L = long_rows(A, S, parts);
   P.fixed = tn.deterministic == 2 && !S.slot32 && row_scales(A, S.long_t, L, P.rexp, P.sexp);
@@ -743,6 +748,10 @@ int upload_csort(Shard &s, const CsortPlan &P) {
                   (rc = s.dev.alloc(&c.xexp_part, P.xexp_part_bytes))))
     return rc;
   if (P.trace_bytes && (rc = s.dev.alloc(&c.trace, P.trace_bytes))) return rc;
+  if (!P.src.empty() && (rc = up(&c.src, P.src))) return rc;  // updatable handles: 4 B per padded entry
+  c.chunks = P.chunks;
+  c.n_slices = P.long_cs.empty() ? 0 : P.long_cs.back();
+  c.long_t = P.long_t;
   c.n_wg = P.n_wg;
   c.H = P.H;
   c.u = P.u;

@@ -92,6 +92,9 @@ struct Tuning {
   int lds_pad = -1;                      // STREAM padded product buffers (-1: by row length, 0 off, 1 on)
   int pf = -1, y_nt = -1, nt = -1;       // row kernels: prefetch, nt y stores, nt col/val
   int dyn_lds = 0;
+  // internal (hspmv_create_updatable; no hspmv_options field): column-sorted
+  // tables are built with their source-index table (CsortPlan::src)
+  int csort_src = 0;
 };
 
 constexpr int kC16Shift = 8;  // 256 nonzeros per column-base block
@@ -249,7 +252,15 @@ struct DevCsort {
   void *part = nullptr, *spart = nullptr;  // partial sums in the slot type
   const uint32_t *long_mask = nullptr;
   const int32_t *long_row = nullptr, *long_cs = nullptr;
+  // Updatable handles only (hspmv_create_updatable; else nullptr): per
+  // entry-stream position, at the position of the entry's VALUE, the CSR index
+  // of the nonzero stored there, kCsortSrcPad for padding (refresh.hip)
+  const uint32_t *src = nullptr;
+  int64_t chunks = 0;    // all workgroups' chunks (blk_c[n_wg])
+  int32_t n_slices = 0;  // long-row slices (long_cs[n_long])
+  int32_t long_t = 0;    // rows above this many nonzeros are long rows (the `extra` term of rexp)
 };
+constexpr uint32_t kCsortSrcPad = 0xFFFFFFFFu;
 
 // Device-side tables the host planner builds once per shard (all optional).
 struct DevPlan {
@@ -385,6 +396,16 @@ hipError_t launch_refresh_slices(int val_dtype, int64_t n_slices, const int32_t 
 // row-pointer arrays slab_rp, m + 1 entries each.
 hipError_t launch_refresh_slabs(int val_dtype, int32_t m, int64_t nnz, int32_t n_slabs, const int32_t *row_ptr,
                                 const int32_t *slab_rp, const void *src, void *dst, hipStream_t st);
+
+// The column-sorted entry stream of an updatable shard (c.src set): every
+// value of c.ent (fp32 records) / c.val (fp64) rewritten from src_val through
+// c.src, scaled by 2^rexp of its row under fixed-point slots; padding 0.
+// Writes the shard's own tables (the views of DevCsort are const for the SpMV).
+hipError_t launch_refresh_csort(int val_dtype, const DevCsort &c, const void *src_val, hipStream_t st);
+// Fixed-point shards: c.rexp and c.sexp restated from src_val (row_scales,
+// hspmv_csort_build.cpp); enqueue it before launch_refresh_csort.
+hipError_t launch_refresh_row_scales(int val_dtype, const DevCsort &c, const int32_t *row_ptr,
+                                     const void *src_val, hipStream_t st);
 
 // ---- multi-vector SpMM (spmm.hip, hspmv_mm.cpp): Y = A X, X row-major n x k
 constexpr int32_t kMmMaxRhs = 32;

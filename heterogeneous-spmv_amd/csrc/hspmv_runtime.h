@@ -338,6 +338,11 @@ struct CsortPlan {
   std::vector<uint32_t> long_mask;
   std::vector<int32_t> long_row, long_cs;  // (empty without long rows)
   std::vector<int16_t> rexp, sexp;         // (empty unless fixed)
+  // Tuning.csort_src only (else empty): per entry-stream position, where the
+  // entry's value is stored (ch * C + at(wide, q, 2), both dtypes), the CSR
+  // index k it came from; kCsortSrcPad for padding
+  std::vector<uint32_t> src;
+  int32_t long_t = 0;                      // rows above this many nonzeros are long rows
   int32_t n_wg = 0, H = 1, u = 16, n_long = 0;
   bool direct = false, nontemporal = true, prefetch = false, slot32 = false, part32 = false, wide = false,
        dyn = false, fixed = false;
@@ -365,9 +370,16 @@ int build_csort(Shard &s, const int32_t *rp, const int32_t *col, const void *val
                 int64_t n, int dtype, unsigned flags);
 
 // ---- hspmv_update.cpp
-// HSPMV_OK when the shard's plan can take new values, else HSPMV_E_INVALID
-// with the message set (the column-sorted kernel).  No device call.
+// Whether the shard's plan can take new values: every plan but a
+// column-sorted one without its source-index table (a handle not created by
+// hspmv_create_updatable).  No device call, no error set.
+bool shard_can_update(const Shard &s);
+// HSPMV_OK when shard_can_update, else HSPMV_E_INVALID with the message set.
 int update_values_why(const Shard &s);
+// HSPMV_E_INVALID when the shard scales its values per row (fixed-point
+// column-sorted slots) and val, its nnz new values in host memory, holds an
+// Inf or NaN: a new handle over them would not be fixed-point.  No device call.
+int update_values_finite(const Shard &s, const void *val);
 // New values for the shard: val = its nnz values in CSR order (host memory,
 // or on_device: on the shard's device); borrowed: the shard reads the
 // caller's device array -- val (NULL: the array as it is) is that array from

@@ -1,6 +1,8 @@
 // hspmv_update.cpp -- new matrix values for a planned shard, in place
 // (hspmv_update_values; see hspmv_runtime.h for the split of the host runtime).
 #include <cstddef>
+#include <cstdint>
+#include <cstring>
 
 #include "hspmv_runtime.h"
 
@@ -13,7 +15,12 @@ namespace hspmv {
 //               and the serial long-row kernels read.  A row-slice shard has
 //               released it, a borrowed one never had it (A.val is the caller's);
 //   row slices  d_sl_val, slice-major (build_slices);
-//   x slabs     d_slab_val, slab-major (build_xslabs); split rows stay in A.val.
+//   x slabs     d_slab_val, slab-major (build_xslabs); split rows stay in A.val;
+//   column-sorted  the entry stream (csort.ent / csort.val), sorted by column
+//               inside each workgroup and, under fixed-point slots, scaled per
+//               row by 2^rexp, which follows the values (build_csort).  Only a
+//               shard that kept the source index of every stream position
+//               (hspmv_create_updatable: csort.src) can restate it.
 // An update puts the new CSR-order values where A.val points -- a copy into
 // d_val, or the caller's array itself for a borrowed shard -- and rebuilds, on
 // the shard's stream, each derived copy the DevPlan launches from
@@ -40,15 +47,53 @@ static int refresh_derived(Shard &s, const void *src) {
       return set_error(HSPMV_E_HIP, "x-slab value refresh on GPU %d failed: %s", s.dev.device,
                        hipGetErrorString(e));
   }
+  if (s.plan.kernel == kCsort) {  // the row scales first: the entry stream is scaled by them
+    hipError_t e = launch_refresh_row_scales(s.val_dtype, s.dp.cs, s.A.row_ptr, src, st);
+    if (e == hipSuccess) e = launch_refresh_csort(s.val_dtype, s.dp.cs, src, st);
+    if (e != hipSuccess)
+      return set_error(HSPMV_E_HIP, "column-sorted value refresh on GPU %d failed: %s", s.dev.device,
+                       hipGetErrorString(e));
+  }
   return HSPMV_OK;
 }
 
+bool shard_can_update(const Shard &s) { return s.plan.kernel != kCsort || s.dp.cs.src != nullptr; }
+
 int update_values_why(const Shard &s) {
-  if (s.plan.kernel == kCsort)
+  if (!shard_can_update(s))
     return set_error(HSPMV_E_INVALID,
                      "the column-sorted kernel's tables cannot take new values (its entries are sorted by "
                      "column inside each block, and the fixed-point row scales follow the values): create the "
-                     "handle with hspmv_options.csort = -1 or deterministic = 1 to update it in place");
+                     "handle with hspmv_options.csort = -1 or deterministic = 1 to update it in place, or "
+                     "with hspmv_create_updatable, which keeps the entries' source indices");
+  return HSPMV_OK;
+}
+
+int update_values_finite(const Shard &s, const void *val) {
+  if (s.plan.kernel != kCsort || !s.dp.cs.fixed || !val) return HSPMV_OK;
+  // an exponent field of all ones: Inf or NaN.  Integer tests under one OR,
+  // no branch in the loop, so it vectorises.
+  unsigned bad = 0;
+  if (s.val_dtype == HSPMV_F32) {
+    const char *v = static_cast<const char *>(val);
+    for (int64_t k = 0; k < s.A.nnz; ++k) {
+      uint32_t b;
+      memcpy(&b, v + 4 * k, 4);
+      bad |= (b & 0x7f800000u) == 0x7f800000u;
+    }
+  } else {
+    const char *v = static_cast<const char *>(val);
+    for (int64_t k = 0; k < s.A.nnz; ++k) {
+      uint64_t b;
+      memcpy(&b, v + 8 * k, 8);
+      bad |= (b & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
+    }
+  }
+  if (bad)
+    return set_error(HSPMV_E_INVALID,
+                     "the new values hold an Inf or NaN and this handle's column-sorted slots are fixed-point "
+                     "(deterministic = 2): a new handle over them would keep fp64 slots, so they cannot be "
+                     "taken in place; create a new handle");
   return HSPMV_OK;
 }
 

@@ -206,6 +206,9 @@ SIGNATURES = {
     "hspmv_get_dtypes": (C.c_int, [_H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hspmv_values_fit_f32": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     "hspmv_update_values": (C.c_int, [_H, _P, C.c_uint]),
+    "hspmv_create_updatable": (C.c_int, [C.POINTER(_H), C.POINTER(Csr), C.POINTER(Csr3Maps),
+                                         C.POINTER(Options), C.c_int]),
+    "hspmv_can_update_values": (C.c_int, [_H]),
     "hspmv_mm_update_values": (C.c_int, [_H, _P, C.c_uint]),
     "hspmv_set_x": (C.c_int, [_H, _P]),
     "hspmv_bind_x_device": (C.c_int, [_H, _P]),

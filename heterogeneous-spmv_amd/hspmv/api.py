@@ -420,7 +420,11 @@ class SpMV:
     handle (hspmv_create_mixed): the values are stored and streamed as float32,
     y is what the float64 operator gives for the widened matrix; one device
     only.  ``op.dtype`` is the vectors' type, ``op.value_dtype`` the stored
-    values'.
+    values'.  ``updatable=True``: the handle takes :meth:`update_values` in
+    every plan, the column-sorted one included (hspmv_create_updatable: such
+    shards keep a source index per stored entry, 4 bytes each, on the device);
+    the plan, ``info`` but for ``device_bytes``, and y are those of the plain
+    handle.  ``op.can_update`` tells whether ``update_values`` would be taken.
     """
 
     def __init__(self, A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, num_gpus: int = 1,
@@ -429,7 +433,7 @@ class SpMV:
                  xcd_remap: Optional[bool] = None, split_rows: bool = True, chunk_u: int = 0,
                  prefetch: Optional[bool] = None, xcd_chunk: int = 0, groups_per_wave: int = 0,
                  col16: Optional[bool] = None, devices: Optional[list] = None,
-                 options: Optional[dict] = None, vector_dtype=None):
+                 options: Optional[dict] = None, vector_dtype=None, updatable: bool = False):
         self.A = A
         self.maps = maps
         self.value_dtype = A.val.dtype
@@ -447,6 +451,19 @@ class SpMV:
         cs = A.c_struct()
         ms = maps.c_struct() if maps is not None else None
         h = C.c_void_p()
+        if updatable:  # every argument as an option: hspmv_create_updatable
+            if num_gpus != 1 and devices is None:
+                n = num_gpus if num_gpus > 0 else device_count()
+                if n < 1:
+                    raise HspmvError("hspmv_create_updatable", -6, "no HIP device visible")
+                devices = list(range(n))
+            opt = _lib.make_options(flags, options, device=0 if device is None else device,
+                                    stream=stream, devices=devices)
+            check(lib().hspmv_create_updatable(C.byref(h), C.byref(cs),
+                                               C.byref(ms) if ms is not None else None, C.byref(opt),
+                                               dtype_code(self.dtype)), "hspmv_create_updatable")
+            self._h = h
+            return
         if self.dtype != self.value_dtype:  # the mixed handle (any other pair: the library refuses)
             if num_gpus != 1 and devices is None:
                 n = num_gpus if num_gpus > 0 else device_count()
@@ -491,11 +508,12 @@ class SpMV:
                     split_rows: bool = True, chunk_u: int = 0,
                     prefetch: Optional[bool] = None, xcd_chunk: int = 0,
                     groups_per_wave: int = 0, col16: Optional[bool] = None,
-                    options: Optional[dict] = None, vector_dtype=None) -> "SpMV":
+                    options: Optional[dict] = None, vector_dtype=None, updatable: bool = False) -> "SpMV":
         """Handle over caller-owned DEVICE arrays (HSPMV_FLAG_DEVICE_PTRS):
         csr_dev/maps_dev hold device pointers; A_meta supplies m, n, dtype.
         ``vector_dtype=np.float64`` over float32 values: the mixed handle (the
-        borrowed val is float32, bound x and y are float64)."""
+        borrowed val is float32, bound x and y are float64).  ``updatable``:
+        as in the constructor."""
         self = cls.__new__(cls)
         self.A = A_meta
         self.maps = None
@@ -508,7 +526,11 @@ class SpMV:
                  | (_lib.FLAG_PREFETCH if prefetch else 0))
         h = C.c_void_p()
         opt = _lib.make_options(flags, options, device=device, stream=stream)
-        if self.dtype != self.value_dtype:
+        if updatable:
+            check(lib().hspmv_create_updatable(C.byref(h), C.byref(csr_dev),
+                                               C.byref(maps_dev) if maps_dev is not None else None,
+                                               C.byref(opt), dtype_code(self.dtype)), "hspmv_create_updatable")
+        elif self.dtype != self.value_dtype:
             check(lib().hspmv_create_mixed(C.byref(h), C.byref(csr_dev),
                                            C.byref(maps_dev) if maps_dev is not None else None,
                                            C.byref(opt), dtype_code(self.dtype)), "hspmv_create_mixed")
@@ -520,6 +542,13 @@ class SpMV:
         return self
 
     # -- new values, same pattern
+    @property
+    def can_update(self) -> bool:
+        """Whether update_values / update_values_device would be taken by this
+        handle's plan (hspmv_can_update_values): False for a column-sorted
+        handle that was not created with ``updatable=True``."""
+        return bool(lib().hspmv_can_update_values(self._h))
+
     def update_values(self, val: np.ndarray) -> None:
         """New matrix values from host memory, in place (hspmv_update_values):
         ``val`` holds nnz values in A's CSR order and casts to ``value_dtype``;

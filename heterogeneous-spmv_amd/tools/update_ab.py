@@ -6,7 +6,9 @@ only alternative before it: destroy + create of the same handle.
            [--cases c3,c3mixed,c5det] [--rounds 5] [--out profiles/update_values/update_ab.jsonl]
 
 In one process, per case (the bench's C3 handle in fp64 and mixed: row slices;
-C5 with deterministic = 1: x slabs), minima over ``--rounds``:
+C5 with deterministic = 1: x slabs; c5csort / c5csort_det2: C5 fp32 with the
+default plan, the column-sorted kernel, and the same with deterministic = 2,
+on a handle from hspmv_create_updatable), minima over ``--rounds``:
   (a) device   update_values_device from a resident device array, HIP events
                on the handle's stream;
   (b) host     update_values from (pageable) host memory, wall time;
@@ -16,8 +18,14 @@ C5 with deterministic = 1: x slabs), minima over ``--rounds``:
                when given, else through this build, whose create path is the
                same code.
 For (a) the line carries the bytes the update reads and writes and what
-fraction of 8 TB/s that is.  After the timed rounds y of the updated handle
-is compared bit for bit with a fresh handle's over the same values.
+fraction of 8 TB/s that is, and for each of (a)-(c) the round-to-round spread
+(max - min).  After the timed rounds y of the updated handle is compared bit
+for bit with a fresh handle's over the same values (a column-sorted handle
+without fixed-point slots adds in atomic order: there the line says whether y
+is within 1e-4 |y| + 1e-5 sum|a x| of it).  The column-sorted cases also run
+hspmv_run of the updatable handle and of a plain one alternately, ``--rounds``
+times each: the same kernel over the same tables, so the difference of the
+minima should stay inside the plain handle's own spread.
 """
 import argparse
 import ctypes as C
@@ -53,6 +61,12 @@ def case(name):
     if name == "c5det":
         A, maps, _ = sweep.build("c5")
         return A, maps, {"options": {"deterministic": 1}}, ("x_slabs", None)
+    if name == "c5csort":
+        A, maps, _ = sweep.build("c5")
+        return A, maps, {"updatable": True}, ("kernel_name", "csort")
+    if name == "c5csort_det2":
+        A, maps, _ = sweep.build("c5")
+        return A, maps, {"updatable": True, "options": {"deterministic": 2}}, ("kernel_name", "csort")
     raise ValueError(name)
 
 
@@ -65,6 +79,17 @@ def update_bytes(A, maps, kw, info):
         rd = A.nnz * sv + 4 * (A.m + 1) + A.m + 8 * (S["n_desc"] + 1)
         return rd, S["padded_entries"] * sv
     rd, wr = A.nnz * sv, A.nnz * sv  # the copy into the CSR-order values
+    if info["kernel_name"] == "csort":
+        # per stored entry (padding included): its source index, the {idx, val}
+        # record read and written (fp64: the value written; the index word read
+        # under fixed-point slots only), and the gathered CSR-order value
+        P = info["csort_chunks"] * 64 * info["chunk_u"]
+        fixed = info["csort_fixed_point"]
+        rd += 4 * P + (8 * P if sv == 4 else (4 * P if fixed else 0)) + A.nnz * sv
+        wr += 8 * P
+        if fixed:  # the row scales: the values and the row pointers once more, rexp written, then gathered
+            rd += A.nnz * sv + 4 * (A.m + 1) + 2 * A.nnz
+            wr += 2 * A.m
     if info["x_slabs"]:
         rd += A.nnz * sv + 4 * (A.m + 1) * (1 + info["x_slabs"])
         wr += A.nnz * sv
@@ -72,7 +97,7 @@ def update_bytes(A, maps, kw, info):
 
 
 def recreate_wall(L, A, maps, kw, rounds):
-    """min wall seconds of destroy + create (+ synchronize) through library L."""
+    """(min, max - min) wall seconds of destroy + create (+ synchronize) through library L."""
     cs, ms = A.c_struct(), maps.c_struct()
     opt = _lib.make_options(0, kw.get("options"), device=0)
     mixed = kw.get("vector_dtype") is not None
@@ -86,15 +111,15 @@ def recreate_wall(L, A, maps, kw, rounds):
         assert rc == 0, L.hspmv_last_error()
         return h
 
-    h, best = create(), 1e30
+    h, ts = create(), []
     for _ in range(rounds):
         tic = time.perf_counter()
         L.hspmv_destroy(h)
         h = create()
         assert L.hspmv_synchronize(h) == 0
-        best = min(best, time.perf_counter() - tic)
+        ts.append(time.perf_counter() - tic)
     L.hspmv_destroy(h)
-    return best
+    return min(ts), max(ts) - min(ts)
 
 
 def main():
@@ -138,10 +163,32 @@ def main():
             op.spmv()
             y = op.get_y()
             assert op.info == info
-        with hspmv.SpMV(hspmv.CsrMatrix(A.m, A.n, A.row_ptr, A.col_idx, v_new), maps, device=0, **kw) as fresh:
-            y_equal = bool(np.array_equal(fresh(x).view(np.uint8), y.view(np.uint8)))
-        t_re = float("nan") if a.no_recreate else \
-            recreate_wall(parent if parent is not None else _lib.lib(), A, maps, kw, a.rounds)
+            run_ab = None
+            if kw.get("updatable"):  # the SpMV itself: this handle against a plain one, alternately
+                plain_kw = {k: v for k, v in kw.items() if k != "updatable"}
+                with hspmv.SpMV(hspmv.CsrMatrix(A.m, A.n, A.row_ptr, A.col_idx, v_new), maps, device=0,
+                                **plain_kw) as plain:
+                    plain.set_x(x)
+                    tu, tp = [], []
+                    for _ in range(a.rounds):
+                        tp.append(plain.run(3, 20)["t_min"])
+                        tu.append(op.run(3, 20)["t_min"])
+                    run_ab = {"updatable_us": round(min(tu) * 1e6, 2), "plain_us": round(min(tp) * 1e6, 2),
+                              "updatable_spread_us": round((max(tu) - min(tu)) * 1e6, 2),
+                              "plain_spread_us": round((max(tp) - min(tp)) * 1e6, 2),
+                              "device_bytes_updatable": info["device_bytes"],
+                              "device_bytes_plain": plain.info["device_bytes"]}
+        fresh_kw = {k: v for k, v in kw.items() if k != "updatable"}
+        with hspmv.SpMV(hspmv.CsrMatrix(A.m, A.n, A.row_ptr, A.col_idx, v_new), maps, device=0, **fresh_kw) as fresh:
+            y_fresh = fresh(x)
+            y_equal = bool(np.array_equal(y_fresh.view(np.uint8), y.view(np.uint8)))
+        y_close = None
+        if not y_equal:
+            rows = np.repeat(np.arange(A.m), np.diff(A.row_ptr))
+            absrow = np.bincount(rows, np.abs(v_new.astype(np.float64)) * np.abs(x[A.col_idx]), minlength=A.m)
+            y_close = bool(np.all(np.abs(y.astype(np.float64) - y_fresh) <= 1e-4 * np.abs(y_fresh) + 1e-5 * absrow))
+        t_re, t_re_spread = (float("nan"), float("nan")) if a.no_recreate else \
+            recreate_wall(parent if parent is not None else _lib.lib(), A, maps, fresh_kw, a.rounds)
         rd, wr = update_bytes(A, maps, kw, info)
         rec = {"case": name, "lib": a.tag or Path(_lib.LIB_PATH).parent.name + "/" + Path(_lib.LIB_PATH).name, "m": A.m, "nnz": A.nnz, "value_dtype": str(A.val.dtype), "vector_dtype": str(np.dtype(xdt)),
                "kernel": info["kernel_name"], "row_slices": info["row_slices"], "x_slabs": info["x_slabs"],
@@ -149,7 +196,10 @@ def main():
                "recreate_ms": None if a.no_recreate else round(t_re * 1e3, 3), "recreate_lib": "parent" if parent is not None else "this",
                "bytes_read": int(rd), "bytes_written": int(wr),
                "device_update_frac_of_8TBps": round((rd + wr) / min(dev) / HBM_PEAK, 4),
-               "rounds": a.rounds, "y_equal_fresh": y_equal}
+               "device_update_spread_us": round((max(dev) - min(dev)) * 1e6, 2),
+               "host_update_spread_ms": round((max(host) - min(host)) * 1e3, 3),
+               "recreate_spread_ms": None if a.no_recreate else round(t_re_spread * 1e3, 3),
+               "rounds": a.rounds, "y_equal_fresh": y_equal, "y_close_fresh": y_close, "run_ab": run_ab}
         out.append(rec)
         print(json.dumps(rec), flush=True)
     if a.out:

@@ -55,7 +55,8 @@ extern "C" {
  * (fp32 values under fp64 vectors): hspmv_create_mixed, hspmv_get_dtypes,
  * hspmv_values_fit_f32, hspmv_slices_plan_vec; new values for a planned
  * handle or operator: hspmv_update_values, hspmv_mm_update_values,
- * HSPMV_VALUES_DEVICE -- functions only, no struct grew. */
+ * HSPMV_VALUES_DEVICE, and for column-sorted handles hspmv_create_updatable,
+ * hspmv_can_update_values -- functions only, no struct grew. */
 
 /* ---------------------------------------------------------------- status */
 #define HSPMV_OK 0
@@ -487,9 +488,11 @@ int hspmv_create_on_device(hspmv_handle **h, const hspmv_csr *A,
  * handle newly created with the same arguments and options from the same
  * pattern with val, on every row and in every supported plan.  The plan, the
  * tables, hspmv_info (device_bytes included) and the sweep phase are untouched:
- * only the values move -- into the CSR-order array, and from there, by two
- * small kernels on the handle's stream, into the row slices' and the x slabs'
- * own copies.
+ * only the values move -- into the CSR-order array, and from there, by small
+ * kernels on the handle's stream, into the row slices' and the x slabs' own
+ * copies and, for a handle from hspmv_create_updatable, into the
+ * column-sorted entry stream (with the fixed-point row scales restated first:
+ * the device tables are then byte for byte a new handle's).
  *
  * flags = 0: val is host memory.  It is consumed before return (hspmv_set_x's
  * rule); works on single-device and sharded handles, shard p taking its range
@@ -508,18 +511,45 @@ int hspmv_create_on_device(hspmv_handle **h, const hspmv_csr *A,
  * HSPMV_E_INVALID, the handle unchanged (every check is made, for every shard,
  * before anything is written): a NULL handle, unknown flag bits, a NULL val
  * on a handle that owns its matrix (nnz > 0), host memory for a borrowed
- * handle, HSPMV_VALUES_DEVICE on a sharded handle, and a handle any shard of
+ * handle, HSPMV_VALUES_DEVICE on a sharded handle, a handle any shard of
  * which runs the column-sorted kernel (hspmv_info.kernel ==
- * HSPMV_KERNEL_CSORT) -- create it with hspmv_options.csort = -1 or
- * deterministic = 1 to update it.  nnz == 0: HSPMV_OK, nothing done.
+ * HSPMV_KERNEL_CSORT) without having been created by hspmv_create_updatable
+ * -- create it with that call, or with hspmv_options.csort = -1 or
+ * deterministic = 1, to update it; hspmv_can_update_values asks beforehand --
+ * and, for host memory, an Inf or NaN among the new values of a handle whose
+ * column-sorted slots are fixed-point (hspmv_info.csort_fixed_point): a new
+ * handle over such values keeps fp64 slots, so no update in place can equal
+ * it.  nnz == 0: HSPMV_OK, nothing done.
+ * Non-finite values from a device pointer are not looked at (that would take
+ * a host synchronisation): keeping them out of a fixed-point column-sorted
+ * handle is the caller's duty.  Indices never depend on values, so the worst
+ * outcome is a non-finite or unspecified y in the rows concerned, never an
+ * access out of range.
  *
- * Not covered: column-sorted handles (their entries are sorted by column
- * inside each block, which only a stored source index per entry could undo,
- * and the fixed-point row scales follow the values); converting the dtype on
- * the way (fp64 input into a mixed handle: narrow it first); a changed
- * pattern; device pointers for sharded handles. */
+ * Not covered: column-sorted handles created by any other call than
+ * hspmv_create_updatable (their entries are sorted by column inside each
+ * block, which only the stored source index per entry undoes); converting the
+ * dtype on the way (fp64 input into a mixed handle: narrow it first); a
+ * changed pattern; device pointers for sharded handles. */
 #define HSPMV_VALUES_DEVICE 1u  /* val is a device pointer on the handle's device */
 int hspmv_update_values(hspmv_handle *h, const void *val, unsigned flags);
+
+/* hspmv_create_mixed -- with vector_dtype == A->dtype: hspmv_create_ex -- whose
+ * handle takes hspmv_update_values in every plan, the column-sorted one
+ * included: every shard that builds column-sorted tables also keeps, on the
+ * device, the CSR index each entry of its (padded) entry stream came from, 4
+ * bytes per stored entry (hspmv_info.csort_chunks * 64 * chunk_u entries).
+ * That memory is why this is a call of its own and not the default.  The
+ * planner's pick, every table the SpMV reads, y and hspmv_info are those of
+ * the handle the other call creates; hspmv_info.device_bytes alone may differ.
+ * Every argument, refusal and error is hspmv_create_mixed's. */
+int hspmv_create_updatable(hspmv_handle **h, const hspmv_csr *A, const hspmv_csr3_maps *maps,
+                           const hspmv_options *opt, int vector_dtype);
+/* 1 when hspmv_update_values would not refuse the handle for its plan (the
+ * rule it applies to every shard: not the column-sorted kernel, or created by
+ * hspmv_create_updatable), else 0; 0 for a NULL handle.  Host only: no device
+ * call, and hspmv_last_error is left alone. */
+int hspmv_can_update_values(const hspmv_handle *h);
 
 /* x (n entries of dtype) from host memory -> every GPU (setX, csrk.cu:92-102,
  * minus the x permutation: matrices are used as given). */
