@@ -8,7 +8,13 @@
 //                          trials of one row-range shard, the checks and the
 //                          timing loop the single- and multi-vector paths share
 //   hspmv_tables.cpp       host planner tables: 16-bit columns, wave tasks,
-//                          x windows, x slabs, split rows, CSR-3 SSR tasks
+//                          x windows, x slabs, split rows, CSR-3 SSR tasks;
+//                          host-only planners (plan_col16, plan_col16g ->
+//                          Col16Plan; plan_xslabs -> XslabPlan; plan_split_rows
+//                          -> SplitPlan; median_serial_len, wants_csort,
+//                          c16_saved_of over SavedTerms), their uploads
+//                          (upload_col16, upload_xslabs, upload_split_rows) and
+//                          the two sequences build_row_tables / build_plan_tables
 //   hspmv_xdict.cpp        block x dictionaries (+ hspmv_xdict_plan), the
 //                          plan entry points' shared preamble (plan_shape)
 //   hspmv_slices.cpp       row slices of dictionary handles (+ hspmv_slices_plan)
@@ -144,7 +150,7 @@ struct Shard {
   int64_t sl_desc_n = 0, sl_padded = 0;  // descriptors, sum of slice widths
   int sl_pos_bits = 0;            // 0 no slices, else 12 or 16 (hspmv_slices_pack)
   int64_t sl_pos_bytes = 0;       // position bytes read per SpMV (the stream and d_sl_ppre)
-  int32_t *d_slab_rp = nullptr;      // x slabs (build_xslabs): per-slab row pointers,
+  int32_t *d_slab_rp = nullptr;      // x slabs (plan_xslabs): per-slab row pointers,
   int32_t *d_slab_col = nullptr;     // slab-major columns and values
   void *d_slab_val = nullptr;
   int32_t n_slabs = 0;
@@ -253,6 +259,65 @@ void build_tasks(const int32_t *rp, int64_t m, const std::vector<int32_t> *inner
                  const std::vector<int32_t> *outer, unsigned flags, const Tuning &tune,
                  std::vector<int32_t> &ts, int *waves);
 bool irregular_gathers(const int32_t *rp, const int32_t *col, int64_t m, double sv);
+// The row kernels' tables are planned on the host apart from their upload:
+// the plan_* functions make no HIP call and touch no Shard, fill a plain
+// struct and return whether the table is taken (dtype: the vectors',
+// val_dtype: the stored values'); the upload_* functions hold the uploads and
+// allocations and set the Shard / DevCSR / DevPlan fields that describe the
+// table, nothing else.  A plan is a local that dies once its upload returns.
+// tools/row_tables_check.cpp decodes every table back into the matrix
+// (make asan-row-tables; tests/test_row_tables_plan.py).
+//
+// 16-bit column offsets (DevCSR.col16 / cbase / cplanes).
+struct Col16Plan {
+  int mode = 1;                  // DevCSR.c16_mode: 1 a base per 2^kC16Shift nonzeros, 2 per row group
+  std::vector<uint16_t> off;     // per nonzero
+  std::vector<int32_t> base;     // per block / group, + 1 pad entry
+  std::vector<uint64_t> planes;  // mode 1: n_planes x plane_words (the last word a pad)
+  int n_planes = 0;
+  int32_t plane_words = 0;
+  int span_bits = 0;  // bits of the widest block's / group's column span (0: not scanned)
+  int shape = 0;      // mode 2: kStream (64-row groups) or kCsr3 (the wave tasks)
+};
+bool plan_col16(const int32_t *col, int64_t nnz, int64_t m, int64_t n, int dtype, int val_dtype,
+                unsigned flags, Col16Plan &P);
+// starts: the CSR-3 wave tasks, or nullptr for STREAM's 64-row groups
+bool plan_col16g(const int32_t *rp, const int32_t *col, int64_t m, int64_t n, int dtype, int val_dtype,
+                 unsigned flags, const Tuning &tune, const std::vector<int32_t> *starts, Col16Plan &P);
+int upload_col16(Shard &s, const Col16Plan &P);
+// x slabs: slab b's row pointers are rp[b * (m + 1) ..], into the slab-major col / val
+struct XslabPlan {
+  int B = 0;
+  std::vector<int32_t> rp, col;
+  std::vector<char> val;  // the stored dtype's bytes
+};
+bool plan_xslabs(const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n, int dtype,
+                 int val_dtype, unsigned flags, const Tuning &tune, XslabPlan &P);
+int upload_xslabs(Shard &s, const XslabPlan &P);
+// split rows (serial order uploads long_row alone)
+struct SplitPlan {
+  std::vector<int32_t> long_row, long_cs{0}, chunk_k;
+  int64_t long_nnz = 0;
+  int32_t long_t = 0;  // split_threshold(flags)
+};
+bool plan_split_rows(const int32_t *rp, int64_t m, unsigned flags, SplitPlan &P);
+int upload_split_rows(Shard &s, const SplitPlan &P);
+int32_t median_serial_len(const int32_t *rp, int64_t m);
+bool wants_csort(const int32_t *rp, const int32_t *col, int64_t m, int64_t n, int dtype, int val_dtype,
+                 unsigned flags, const Tuning &tune);
+// What a launch reads instead of the 32-bit CSR streams, and the numbers the
+// bytes it saves are worked out from (c16_saved_of: Shard::c16_saved).
+enum SavedFormat { kFmtCol32 = 0, kFmtCsort, kFmtSlices, kFmtDict, kFmtGroup16, kFmtBlock16, kFmtSlabs };
+struct SavedTerms {
+  int dtype = HSPMV_F64, val_dtype = HSPMV_F64;
+  int64_t m = 0, nnz = 0, long_nnz = 0, x_entries = 0;
+  double csort_format_bytes = 0.0;                      // kFmtCsort
+  int64_t sl_padded = 0, sl_pos_bytes = 0, sl_desc_n = 0;  // kFmtSlices
+  int64_t xd_runs_n = 0, xd_entries = 0, blocks = 0;    // kFmtSlices, kFmtDict
+  int64_t groups = 0;                                   // kFmtGroup16: the bases read
+  int n_cplanes = 0, n_slabs = 0;                       // kFmtBlock16; kFmtSlabs
+};
+double c16_saved_of(int format, const SavedTerms &t);
 // (the vectors' and the values' dtypes: s.dtype, s.val_dtype)
 int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
                      int64_t n, unsigned flags);

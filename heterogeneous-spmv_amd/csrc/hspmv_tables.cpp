@@ -33,15 +33,25 @@ int64_t count_distinct_cols(const int32_t *col, int64_t nnz, int64_t n) {
 constexpr int kMaxC16Planes = 1;
 constexpr int kMaxC16PlanesForced = 8;  // 3 index bytes: still fewer than 4
 
-int build_col16(Shard &s, const int32_t *col, int64_t nnz, int64_t m, int64_t n, int dtype,
-                unsigned flags, bool *used) {
-  *used = false;
-  if (nnz == 0) return HSPMV_OK;
+// Bits of a column span: the planner's gather-regularity hint (DevCSR.col_span_bits).
+static int span_bits_of(int32_t maxspan) {
+  int bits = 0;
+  while (bits < 31 && (int64_t(1) << bits) <= maxspan) ++bits;
+  return std::max(1, bits);
+}
+
+// P.span_bits is set as soon as the spans are scanned, also where the table
+// is then declined (NO_COL16, too many planes).
+bool plan_col16(const int32_t *col, int64_t nnz, int64_t m, int64_t n, int dtype, int val_dtype,
+                unsigned flags, Col16Plan &P) {
+  P = Col16Plan();
+  if (nnz == 0) return false;
   const bool forced = (flags & HSPMV_FLAG_COL16) != 0 && !(flags & HSPMV_FLAG_NO_COL16);
-  if (!forced && mall_resident(m, n, nnz, dtype, s.val_dtype)) return HSPMV_OK;
+  if (!forced && mall_resident(m, n, nnz, dtype, val_dtype)) return false;
   const int64_t B = int64_t(1) << kC16Shift;
   const int64_t nb = (nnz + B - 1) / B;
-  std::vector<int32_t> base((size_t)nb + 1, 0);  // +1: kernels load bases in pairs
+  std::vector<int32_t> &base = P.base;
+  base.assign((size_t)nb + 1, 0);  // +1: kernels load bases in pairs
   std::vector<int32_t> span((size_t)nb, 0);
   parallel_ranges(nb, 4096, [&](int64_t b0, int64_t b1, int) {
     for (int64_t b = b0; b < b1; ++b) {
@@ -57,15 +67,17 @@ int build_col16(Shard &s, const int32_t *col, int64_t nnz, int64_t m, int64_t n,
   });
   int32_t maxspan = 0;
   for (int32_t v : span) maxspan = std::max(maxspan, v);
-  int bits = 0;
-  while (bits < 31 && (int64_t(1) << bits) <= maxspan) ++bits;
-  s.A.col_span_bits = std::max(1, bits);  // the planner's gather-regularity hint
-  if (flags & HSPMV_FLAG_NO_COL16) return HSPMV_OK;
-  const int planes = std::max(0, bits - 16);
-  if (planes > (forced ? kMaxC16PlanesForced : kMaxC16Planes)) return HSPMV_OK;
+  P.span_bits = span_bits_of(maxspan);
+  if (flags & HSPMV_FLAG_NO_COL16) return false;
+  const int planes = std::max(0, P.span_bits - 16);
+  if (planes > (forced ? kMaxC16PlanesForced : kMaxC16Planes)) return false;
   const int64_t nw = (nnz + 63) / 64 + 1;  // +1: kernels load words in pairs
-  std::vector<uint16_t> off((size_t)nnz);
-  std::vector<uint64_t> pl((size_t)(planes * nw), 0);
+  P.n_planes = planes;
+  P.plane_words = (int32_t)nw;
+  std::vector<uint16_t> &off = P.off;
+  std::vector<uint64_t> &pl = P.planes;
+  off.resize((size_t)nnz);
+  pl.assign((size_t)(planes * nw), 0);
   parallel_ranges(nb, 4096, [&](int64_t b0, int64_t b1, int) {
     // blocks are 4 words wide, so threads never share a plane word
     for (int64_t b = b0; b < b1; ++b) {
@@ -78,16 +90,22 @@ int build_col16(Shard &s, const int32_t *col, int64_t nnz, int64_t m, int64_t n,
       }
     }
   });
+  return true;
+}
+
+// Either kind of 16-bit columns (plan_col16, plan_col16g) onto the device.
+int upload_col16(Shard &s, const Col16Plan &P) {
   int rc;
-  if ((rc = s.dev.upload(&s.d_c16, off.data(), 2 * off.size()))) return rc;
-  if ((rc = s.dev.upload(&s.d_cbase, base.data(), 4 * base.size()))) return rc;
-  if (planes && (rc = s.dev.upload(&s.d_cplanes, pl.data(), 8 * pl.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_c16, P.off.data(), 2 * P.off.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_cbase, P.base.data(), 4 * P.base.size()))) return rc;
+  if (P.n_planes && (rc = s.dev.upload(&s.d_cplanes, P.planes.data(), 8 * P.planes.size()))) return rc;
   s.A.col16 = s.d_c16;
   s.A.cbase = s.d_cbase;
   s.A.cplanes = s.d_cplanes;
-  s.A.n_cplanes = planes;
-  s.A.cplane_words = (int32_t)nw;
-  *used = true;
+  s.A.n_cplanes = P.n_planes;
+  s.A.cplane_words = P.plane_words;
+  s.A.c16_mode = P.mode;
+  s.c16g_shape = P.shape;
   return HSPMV_OK;
 }
 
@@ -95,30 +113,31 @@ int build_col16(Shard &s, const int32_t *col, int64_t nnz, int64_t m, int64_t n,
 // columns span < 65536, col = base[g] + off16 with one int32 base per
 // group -- 2 instead of 4 index bytes per nonzero for one scalar load per
 // group and one add per element, none of the per-256-nonzero base pairs,
-// selects and planes of build_col16.  Auto: Infinity-Cache-resident
+// selects and planes of plan_col16.  Auto: Infinity-Cache-resident
 // matrices (C2: 15.56 -> 15.12 us in one process, bench 724-732 -> 754
-// GFLOP/s); HBM-resident ones keep build_col16's blocks (C4 53.0 vs 55.4
+// GFLOP/s); HBM-resident ones keep plan_col16's blocks (C4 53.0 vs 55.4
 // us with group bases, c3h/l4k within 1 %; profiles/r01_ab_col16_group*.jsonl).
 // Tuning.col16_group = -1 disables, 1 uses it whenever it fits.  Split rows (read
 // by the split-row kernels from the 32-bit columns) get offset 0.
 // Row groups: STREAM's 64-row groups (starts == nullptr) or the packed CSR3
 // wave tasks [starts[g], starts[g+1]).
-int build_col16g(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int64_t n, int dtype,
-                 unsigned flags, const std::vector<int32_t> *starts, bool *used) {
-  *used = false;
-  const int mode = s.tune.col16_group;  // -1 off, 0 auto, 1 on whenever it fits
+bool plan_col16g(const int32_t *rp, const int32_t *col, int64_t m, int64_t n, int dtype, int val_dtype,
+                 unsigned flags, const Tuning &tune, const std::vector<int32_t> *starts, Col16Plan &P) {
+  P = Col16Plan();
+  const int mode = tune.col16_group;  // -1 off, 0 auto, 1 on whenever it fits
   const int64_t nnz = rp[m];
-  if (mode < 0 || (flags & HSPMV_FLAG_NO_COL16) || nnz == 0) return HSPMV_OK;
+  if (mode < 0 || (flags & HSPMV_FLAG_NO_COL16) || nnz == 0) return false;
   const bool forced = (flags & HSPMV_FLAG_COL16) != 0 || mode == 1;
-  if (!forced && !mall_resident(m, n, nnz, dtype, s.val_dtype)) return HSPMV_OK;
+  if (!forced && !mall_resident(m, n, nnz, dtype, val_dtype)) return false;
   const int32_t long_t = split_threshold(flags);
   const int64_t ng = starts ? (int64_t)starts->size() - 1 : (m + 63) / 64;
-  if (ng <= 0) return HSPMV_OK;
+  if (ng <= 0) return false;
   auto rows = [&](int64_t g, int64_t &r0, int64_t &r1) {
     r0 = starts ? (*starts)[(size_t)g] : 64 * g;
     r1 = starts ? (*starts)[(size_t)g + 1] : std::min(m, 64 * g + 64);
   };
-  std::vector<int32_t> base((size_t)ng + 1, 0);  // +1: read by 8-byte scalar loads
+  std::vector<int32_t> &base = P.base;
+  base.assign((size_t)ng + 1, 0);  // +1: read by 8-byte scalar loads
   std::vector<int32_t> span((size_t)ng, 0);
   parallel_ranges(ng, 4096, [&](int64_t g0, int64_t g1, int) {
     for (int64_t g = g0; g < g1; ++g) {
@@ -138,8 +157,9 @@ int build_col16g(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int
   });
   int32_t maxspan = 0;
   for (int32_t v : span) maxspan = std::max(maxspan, v);
-  if (maxspan > 65535) return HSPMV_OK;
-  std::vector<uint16_t> off((size_t)nnz, 0);
+  if (maxspan > 65535) return false;
+  std::vector<uint16_t> &off = P.off;
+  off.assign((size_t)nnz, 0);
   parallel_ranges(ng, 4096, [&](int64_t g0, int64_t g1, int) {
     for (int64_t g = g0; g < g1; ++g) {
       int64_t ra, rb;
@@ -150,20 +170,10 @@ int build_col16g(Shard &s, const int32_t *rp, const int32_t *col, int64_t m, int
       }
     }
   });
-  int rc;
-  if ((rc = s.dev.upload(&s.d_c16, off.data(), 2 * off.size()))) return rc;
-  if ((rc = s.dev.upload(&s.d_cbase, base.data(), 4 * base.size()))) return rc;
-  int bits = 0;
-  while (bits < 31 && (int64_t(1) << bits) <= maxspan) ++bits;
-  s.A.col_span_bits = std::max(1, bits);
-  s.A.col16 = s.d_c16;
-  s.A.cbase = s.d_cbase;
-  s.A.cplanes = nullptr;
-  s.A.n_cplanes = 0;
-  s.A.c16_mode = 2;
-  s.c16g_shape = starts ? kCsr3 : kStream;
-  *used = true;
-  return HSPMV_OK;
+  P.mode = 2;
+  P.span_bits = span_bits_of(maxspan);
+  P.shape = starts ? kCsr3 : kStream;
+  return true;
 }
 
 // CSR-3 task packing (the default CSR-3 plan): the super-rows of the inner
@@ -519,40 +529,41 @@ double median_group_span(const int32_t *rp, const int32_t *col, int64_t m) {
 constexpr double kSlabBytes = 2.0 * 1024 * 1024;
 constexpr int kMaxSlabs = 32;
 
-int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
-                 int64_t n, int dtype, unsigned flags) {
+bool plan_xslabs(const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n, int dtype,
+                 int val_dtype, unsigned flags, const Tuning &tune, XslabPlan &P) {
   // sv: an x / y entry (the slab width, the passes' y traffic, the gathers);
   // sval: a stored value (the matrix stream, the slab-major copy)
-  const double sval = (double)dtype_size(s.val_dtype);
-  s.n_slabs = 0;
-  const int forced = s.tune.x_slabs < 0 ? 0 : (s.tune.x_slabs > 0 ? s.tune.x_slabs : -1);  // -1 auto, 0 off, B slabs
-  if (forced == 0 || !val || m == 0 || n == 0 || flag_kernel(flags) == kVector) return HSPMV_OK;
+  const double sval = (double)dtype_size(val_dtype);
+  P = XslabPlan();
+  const int forced = tune.x_slabs < 0 ? 0 : (tune.x_slabs > 0 ? tune.x_slabs : -1);  // -1 auto, 0 off, B slabs
+  if (forced == 0 || !val || m == 0 || n == 0 || flag_kernel(flags) == kVector) return false;
   const int64_t nnz = rp[m];
   const double sv = (double)dtype_size(dtype);
-  const double slab_bytes = s.tune.xslab_bytes > 0 ? std::max(4096.0, s.tune.xslab_bytes) : kSlabBytes;
+  const double slab_bytes = tune.xslab_bytes > 0 ? std::max(4096.0, tune.xslab_bytes) : kSlabBytes;
   int B = forced > 0 ? forced : (int)std::ceil((double)n * sv / slab_bytes);
   B = (int)std::min<int64_t>(std::min(B, kMaxSlabs), n);
-  if (B < 2) return HSPMV_OK;
+  if (B < 2) return false;
   const int32_t long_t = split_threshold(flags);
   const int64_t W = (n + B - 1) / B;  // columns per slab
   if (forced < 0) {
-    if (mall_resident(m, n, nnz, dtype, s.val_dtype) || (double)n * sv <= kXcdL2Bytes) return HSPMV_OK;
+    if (mall_resident(m, n, nnz, dtype, val_dtype) || (double)n * sv <= kXcdL2Bytes) return false;
     // the passes must pay: every extra one re-reads a row-pointer array and
     // y and rewrites y (at most a quarter of the matrix stream in total),
     // and each pass must stream millions of nonzeros (a launch is ~2-5 us)
     const double extra = (double)(B - 1) * (4.0 * (double)(m + 1) + 2.0 * sv * (double)m);
-    if (extra > 0.25 * (double)nnz * (sval + 4.0) || (double)nnz / B < 2.0e6) return HSPMV_OK;
-    if (!irregular_gathers(rp, col, m, sv)) return HSPMV_OK;
+    if (extra > 0.25 * (double)nnz * (sval + 4.0) || (double)nnz / B < 2.0e6) return false;
+    if (!irregular_gathers(rp, col, m, sv)) return false;
     // ... and only when the x a row group gathers from is wider than an
     // XCD's L2 (median 64-row group column span > 4 MiB of x): scattered but
     // local gathers (a +-4000 band of random columns, `mix`) stay L2 hits
     // without slabs, and the extra passes only cost (deterministic handles
     // on mix: 284 us with four slabs vs 209 without; profiles/r04/
     // sweep_deterministic.jsonl)
-    if (median_group_span(rp, col, m) * sv <= kXcdL2Bytes) return HSPMV_OK;
+    if (median_group_span(rp, col, m) * sv <= kXcdL2Bytes) return false;
   }
   // per (slab, row) segment lengths; rows must be slab-monotone
-  std::vector<int32_t> srp((size_t)B * (size_t)(m + 1), 0);
+  std::vector<int32_t> &srp = P.rp;
+  srp.assign((size_t)B * (size_t)(m + 1), 0);
   std::atomic<bool> unsorted{false};
   parallel_ranges(m, 65536, [&](int64_t ra, int64_t rb, int) {
     for (int64_t r = ra; r < rb; ++r) {
@@ -567,7 +578,7 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
       }
     }
   });
-  if (unsorted) return HSPMV_OK;
+  if (unsorted) return false;
   int64_t base = 0;  // slab-major offsets
   for (int b = 0; b < B; ++b) {
     int32_t *p = srp.data() + (size_t)b * (size_t)(m + 1);
@@ -576,8 +587,10 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
     base = p[m];
   }
   const int64_t snnz = base;  // in-kernel nonzeros (split rows excluded)
-  std::vector<int32_t> scol((size_t)std::max<int64_t>(snnz, 1));
-  std::vector<char> svals((size_t)std::max<int64_t>(snnz, 1) * (size_t)sval);
+  std::vector<int32_t> &scol = P.col;
+  std::vector<char> &svals = P.val;
+  scol.resize((size_t)std::max<int64_t>(snnz, 1));
+  svals.resize((size_t)std::max<int64_t>(snnz, 1) * (size_t)sval);
   parallel_ranges(m, 65536, [&](int64_t ra, int64_t rb, int) {
     for (int64_t r = ra; r < rb; ++r) {
       const int32_t k0 = rp[r], k1 = rp[r + 1];
@@ -593,11 +606,17 @@ int build_xslabs(Shard &s, const int32_t *rp, const int32_t *col, const void *va
       }
     }
   });
+  P.B = B;
+  return true;
+}
+
+int upload_xslabs(Shard &s, const XslabPlan &P) {
   int rc;
-  if ((rc = s.dev.upload(&s.d_slab_rp, srp.data(), 4 * srp.size()))) return rc;
-  if ((rc = s.dev.upload(&s.d_slab_col, scol.data(), 4 * scol.size()))) return rc;
-  if ((rc = s.dev.upload(&s.d_slab_val, svals.data(), svals.size()))) return rc;
-  s.n_slabs = B;
+  if ((rc = s.dev.upload(&s.d_slab_rp, P.rp.data(), 4 * P.rp.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_slab_col, P.col.data(), 4 * P.col.size()))) return rc;
+  if ((rc = s.dev.upload(&s.d_slab_val, P.val.data(), P.val.size()))) return rc;
+  s.n_slabs = P.B;
+  s.A.n_slabs = P.B;
   return HSPMV_OK;
 }
 
@@ -621,29 +640,61 @@ void slab_kernel_rule(Shard &s, const int32_t *rp, int64_t m, unsigned flags) {
   s.A.slab_stream = s.heavy_frac < kSlabHeavyShare;
 }
 
+// The typical serially summed row (median length of the rows of 1..40
+// nonzeros, kSerialMax; 0 without such rows): the planner's LDS bank rule.
+int32_t median_serial_len(const int32_t *rp, int64_t m) {
+  constexpr int kSerial = kSerialMax;
+  int64_t hist[kSerial + 1] = {0}, tot = 0;
+  for (int64_t r = 0; r < m; ++r) {
+    const int64_t len = rp[r + 1] - rp[r];
+    if (len >= 1 && len <= kSerial) {
+      ++hist[len];
+      ++tot;
+    }
+  }
+  int32_t med = 0;
+  for (int64_t acc = 0; med < kSerial && 2 * acc < tot;) acc += hist[++med];
+  return tot ? med : 0;
+}
+
+// Whether the shard asks for the column-sorted tables (build_csort may still
+// decline): the forced kernel, Tuning.csort = 1 (whenever it can be built,
+// -1 off), or the auto rule.
+bool wants_csort(const int32_t *rp, const int32_t *col, int64_t m, int64_t n, int dtype, int val_dtype,
+                 unsigned flags, const Tuning &tune) {
+  const unsigned kf = flag_kernel(flags);
+  const int cm = tune.csort;
+  const double sv = (double)dtype_size(dtype);
+  // an ordered or serial handle (deterministic = 1, 3) never builds the
+  // csort tables: the planner would pick kCsort whenever they exist
+  // (plan_launch); a reproducible one (2) builds them with fixed-point slots
+  // ... and neither does a mixed handle (fp32 values under fp64 vectors):
+  // csort has no such tables, so it plans as an ordered one
+  const bool ordered = tune.deterministic == 1 || tune.deterministic == 3 || val_dtype != dtype;
+  if (ordered) return false;
+  if (kf == kCsort || cm == 1) return true;
+  // Scattered gathers from an x the L1 cannot hold go to the L2 one line
+  // per nonzero, at its request rate, whatever the L2's capacity: until r04
+  // the rule also asked for x beyond an XCD's 4 MiB L2, which kept fp32
+  // `mix` (x = 3.8 MiB, random columns within +-4000) on the CSR3 kernel
+  // at 90.8 us against csort's 62.5 (profiles/r04/auto_regret_f32.jsonl);
+  // x of a few L1s (the zoo's `tall`, 16-32 KiB) stays on the row kernels.
+  return kf == kAuto && cm == 0 && tune.x_slabs == 0 && !mall_resident(m, n, rp[m], dtype, val_dtype) &&
+         (double)n * sv > 256.0 * 1024 && irregular_gathers(rp, col, m, sv);
+}
+
 // Host-side tables that need the columns (built at upload, while they are
-// at hand): the CSR-3 packed tasks, the block x dictionaries, and (without
-// dictionaries) the 16-bit column offsets and the x windows of both row
-// kernels.
+// at hand), in this order, the first of csort, slabs and dictionaries that is
+// taken ending the sequence: the wave tasks; the column-sorted tables; the x
+// slabs; the x windows of both row kernels; the block x dictionaries; the
+// 16-bit columns, group bases for the handle's row kernel before block bases.
+// Each plan is a local that dies with its upload.  col_span_bits is the
+// planner's gather-regularity hint: 31 where the kernel gathers from all of
+// x, 1 with dictionaries, else what the 16-bit column planners scanned.
 int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
                      int64_t n, unsigned flags) {
-  const int dtype = s.dtype;  // the vectors'; the values': s.val_dtype
-  // the typical serially summed row (median length of the rows of 1..40
-  // nonzeros, kSerialMax): the planner's LDS bank rule
-  {
-    constexpr int kSerial = kSerialMax;
-    int64_t hist[kSerial + 1] = {0}, tot = 0;
-    for (int64_t r = 0; r < m; ++r) {
-      const int64_t len = rp[r + 1] - rp[r];
-      if (len >= 1 && len <= kSerial) {
-        ++hist[len];
-        ++tot;
-      }
-    }
-    int32_t med = 0;
-    for (int64_t acc = 0; med < kSerial && 2 * acc < tot;) acc += hist[++med];
-    s.A.serial_len = tot ? med : 0;
-  }
+  const int dtype = s.dtype, val_dtype = s.val_dtype;  // the vectors'; the stored values'
+  s.A.serial_len = median_serial_len(rp, m);
   int waves = 4;
   build_tasks(rp, m, s.A.n_ssr > 0 ? &s.h_inner : nullptr, s.A.n_ssr > 0 ? &s.h_outer : nullptr,
               flags, s.tune, s.h_tasks, &waves);
@@ -651,48 +702,28 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
   s.h_xwin.clear();
   s.h_xwin_t.clear();
   int rc;
-  {
-    const unsigned kf = flag_kernel(flags);
-    const int cm = s.tune.csort;  // -1 off, 0 auto, 1 whenever it can be built
-    const double sv = (double)dtype_size(dtype);
-    // an ordered or serial handle (deterministic = 1, 3) never builds the
-    // csort tables: the planner would pick kCsort whenever they exist
-    // (plan_launch); a reproducible one (2) builds them with fixed-point slots
-    // ... and neither does a mixed handle (fp32 values under fp64 vectors):
-    // csort has no such tables, so it plans as an ordered one
-    const bool ordered = s.tune.deterministic == 1 || s.tune.deterministic == 3 || s.val_dtype != dtype;
-    bool want = !ordered && (kf == kCsort || cm == 1);
-    // Scattered gathers from an x the L1 cannot hold go to the L2 one line
-    // per nonzero, at its request rate, whatever the L2's capacity: until r04
-    // the rule also asked for x beyond an XCD's 4 MiB L2, which kept fp32
-    // `mix` (x = 3.8 MiB, random columns within +-4000) on the CSR3 kernel
-    // at 90.8 us against csort's 62.5 (profiles/r04/auto_regret_f32.jsonl);
-    // x of a few L1s (the zoo's `tall`, 16-32 KiB) stays on the row kernels.
-    if (!want && kf == kAuto && cm == 0 && !ordered && s.tune.x_slabs == 0 &&
-        !mall_resident(m, n, rp[m], dtype, s.val_dtype) && (double)n * sv > 256.0 * 1024)
-      want = irregular_gathers(rp, col, m, sv);
-    if (want) {
-      if ((rc = build_csort(s, rp, col, val, m, n, dtype, flags))) return rc;
-      if (s.A.has_csort) {
-        s.A.col_span_bits = 31;
-        return HSPMV_OK;
-      }
+  if (wants_csort(rp, col, m, n, dtype, val_dtype, flags, s.tune)) {
+    if ((rc = build_csort(s, rp, col, val, m, n, dtype, flags))) return rc;
+    if (s.A.has_csort) {
+      s.A.col_span_bits = 31;
+      return HSPMV_OK;
     }
   }
-  if ((rc = build_xslabs(s, rp, col, val, m, n, dtype, flags))) return rc;
-  if (s.n_slabs) {  // slab passes read 32-bit columns from global x
-    s.A.col_span_bits = 31;
-    s.A.n_slabs = s.n_slabs;
-    if (!s.h_tasks.empty()) slab_kernel_rule(s, rp, m, flags);
-    return HSPMV_OK;
+  {
+    XslabPlan X;
+    if (plan_xslabs(rp, col, val, m, n, dtype, val_dtype, flags, s.tune, X)) {
+      if ((rc = upload_xslabs(s, X))) return rc;
+      s.A.col_span_bits = 31;  // slab passes read 32-bit columns from global x
+      if (!s.h_tasks.empty()) slab_kernel_rule(s, rp, m, flags);
+      return HSPMV_OK;
+    }
   }
   s.h_xwin = xwin_table(rp, col, m, nullptr, s.tune);
-  s.h_xwin_t.clear();
   if (!s.h_tasks.empty()) s.h_xwin_t = xwin_table(rp, col, m, &s.h_tasks, s.tune);
   const int kern = kernel_for_tables(s.A.n_ssr, !s.h_tasks.empty(), flags);
   const bool have_xwin = kern == kCsr3 ? !s.h_xwin_t.empty() : !s.h_xwin.empty();
   if ((rc = build_xdict(s, rp, col, val, m, n, flags, have_xwin))) return rc;
-  if (s.xd_shape) {  // col_span_bits: the planner's gather-regularity hint
+  if (s.xd_shape) {
     s.h_xwin.clear();
     s.h_xwin_t.clear();
     s.A.col_span_bits = 1;
@@ -701,162 +732,202 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
     return HSPMV_OK;
   }
   s.A.has_xwin = !s.h_xwin.empty();
-  bool c16 = false;
-  if (kern == kStream && (rc = build_col16g(s, rp, col, m, n, dtype, flags, nullptr, &c16))) return rc;
-  if (kern == kCsr3 && (rc = build_col16g(s, rp, col, m, n, dtype, flags, &s.h_tasks, &c16))) return rc;
-  if (!c16 && (rc = build_col16(s, col, rp[m], m, n, dtype, flags, &c16))) return rc;
+  Col16Plan C;
+  bool c16 = (kern == kStream || kern == kCsr3) &&
+             plan_col16g(rp, col, m, n, dtype, val_dtype, flags, s.tune, kern == kCsr3 ? &s.h_tasks : nullptr, C);
+  if (!c16) c16 = plan_col16(col, rp[m], m, n, dtype, val_dtype, flags, C);
+  if (C.span_bits) s.A.col_span_bits = C.span_bits;
+  return c16 ? upload_col16(s, C) : HSPMV_OK;
+}
+
+// Split rows: rows longer than split_threshold(flags), cut into kLongChunk
+// pieces [chunk_k[2c], chunk_k[2c+1]); long_cs is the prefix of the rows'
+// chunk counts.  False without such rows.
+bool plan_split_rows(const int32_t *rp, int64_t m, unsigned flags, SplitPlan &P) {
+  P = SplitPlan();
+  P.long_t = split_threshold(flags);
+  for (int64_t r = 0; r < m; ++r) {
+    const int32_t b = rp[r], e = rp[r + 1];
+    if (e - b <= P.long_t) continue;
+    P.long_nnz += e - b;
+    P.long_row.push_back((int32_t)r);
+    for (int32_t k = b; k < e; k += kLongChunk) {
+      P.chunk_k.push_back(k);
+      P.chunk_k.push_back(e - k > kLongChunk ? k + kLongChunk : e);
+    }
+    P.long_cs.push_back((int32_t)(P.chunk_k.size() / 2));
+  }
+  return !P.long_row.empty();
+}
+
+// The split rows onto the device.  Chunked: a partial sum per chunk, added
+// per row by a second kernel.  Serial order (dp.serial_max == INT32_MAX): one
+// workgroup per row on a stream of its own, so only long_row is read; the
+// partials are the rows' sums, scattered into y after the row kernel.
+int upload_split_rows(Shard &s, const SplitPlan &P) {
+  const bool serial = s.dp.serial_max == INT32_MAX;
+  const size_t nl = P.long_row.size(), nc = serial ? 0 : P.chunk_k.size() / 2;
+  int rc;
+  if ((rc = s.dev.upload(&s.d_long_row, P.long_row.data(), 4 * nl))) return rc;
+  if (!serial && ((rc = s.dev.upload(&s.d_long_cstart, P.long_cs.data(), 4 * P.long_cs.size())) ||
+                  (rc = s.dev.upload(&s.d_chunk_k, P.chunk_k.data(), 4 * P.chunk_k.size()))))
+    return rc;
+  if ((rc = s.dev.alloc(&s.d_partials, dtype_size(s.dtype) * (serial ? nl : nc)))) return rc;
+  s.dp.long_t = P.long_t;
+  s.dp.n_long = (int32_t)nl;
+  s.dp.n_chunks = (int32_t)nc;
+  s.dp.long_row = s.d_long_row;
+  s.dp.long_cstart = s.d_long_cstart;
+  s.dp.chunk_k = s.d_chunk_k;
+  s.dp.partials = s.d_partials;
+  s.dp.long_serial = serial;
+  if (serial && ((rc = s.dev.new_stream(&s.dp.long_stream)) || (rc = s.dev.new_event(&s.dp.long_fork)) ||
+                 (rc = s.dev.new_event(&s.dp.long_join))))
+    return rc;
   return HSPMV_OK;
 }
 
-// Host planner tables for one shard (needs s.h_rp): split rows (rows longer
-// than kLongRow, cut into kLongChunk pieces), and the device copies of the
-// tables build_row_tables planned (wave tasks, x windows).
-int build_plan_tables(Shard &s, unsigned flags) {
-  const int dtype = s.dtype;  // the vectors' (serial bound, partials); the values': s.val_dtype
-  const std::vector<int32_t> &rp = s.h_rp;
-  const int64_t m = s.A.m;
-  s.dp = DevPlan();
-  s.dp.serial_max = dtype == HSPMV_F32 ? kSerialMaxF32 : kSerialMax;
-  if (s.tune.deterministic == HSPMV_DETERMINISTIC_SERIAL) {  // every row by one lane, in order
-    if (s.plan.kernel != kStream && s.plan.kernel != kCsr3)
-      return set_error(HSPMV_E_INVALID, "deterministic = 3 (serial order) needs the row kernels, and "
-                                        "they cannot address this matrix (32-bit offsets)");
-    s.dp.serial_max = INT32_MAX;
-  } else if (s.tune.serial_max > 0) {
-    s.dp.serial_max = s.tune.serial_max;  // A/B knob (HSPMV_SERIAL_MAX, diagnostic builds)
+// Bytes per SpMV that the launch's format saves against the 32-bit CSR
+// streams (hspmv_info.col16_bytes_saved; negative: it costs).
+double c16_saved_of(int format, const SavedTerms &t) {
+  const double sv = (double)dtype_size(t.dtype), sval = (double)dtype_size(t.val_dtype);
+  const int64_t m = t.m;
+  switch (format) {
+    case kFmtCsort:
+      return alg_bytes_of(t.m, t.x_entries, t.nnz, t.dtype, t.val_dtype, 0, 0) - t.csort_format_bytes;
+    case kFmtSlices:  // the slice-major streams instead of the CSR-order ones and the row pointers
+      return (double)t.nnz * (sval + 4.0) + 4.0 * (double)(m + 1) -
+             (64.0 * (double)t.sl_padded * sval + (double)t.sl_pos_bytes + (double)m +
+              8.0 * (double)(t.sl_desc_n + 1)) -
+             4.0 * (double)(t.xd_runs_n * 2) - 4.0 * (double)t.blocks -
+             sv * (double)(t.xd_entries - t.x_entries);
+    case kFmtDict:
+      // index bytes: 2 instead of 4 per in-kernel nonzero, plus the tables;
+      // x: the staged entries instead of the distinct columns
+      return 2.0 * (double)(t.nnz - t.long_nnz) - 4.0 * (double)(t.xd_runs_n * 2) -
+             4.0 * (double)t.blocks - sv * (double)(t.xd_entries - t.x_entries);
+    case kFmtGroup16:
+      return 2.0 * (double)(t.nnz - t.long_nnz) - 4.0 * (double)t.groups;
+    case kFmtBlock16: {
+      const int64_t nb = (t.nnz + (int64_t(1) << kC16Shift) - 1) >> kC16Shift;
+      return 2.0 * (double)(t.nnz - t.long_nnz) - 4.0 * (double)nb -
+             (double)t.n_cplanes * (double)(t.nnz - t.long_nnz) / 8.0;
+    }
+    case kFmtSlabs:  // per extra pass: one more row-pointer array, and y read back + rewritten
+      return -(double)(t.n_slabs - 1) * (4.0 * (double)(m + 1) + 2.0 * sv * (double)m);
   }
-  int64_t long_nnz = 0;
-  if (s.plan.kernel == kCsort) {  // long rows are slices of the csort blocks
+  return 0.0;
+}
+
+static SavedTerms saved_terms(const Shard &s, int64_t long_nnz) {
+  SavedTerms t;
+  t.dtype = s.dtype, t.val_dtype = s.val_dtype;
+  t.m = s.A.m, t.nnz = s.A.nnz, t.long_nnz = long_nnz, t.x_entries = s.x_entries;
+  t.csort_format_bytes = s.csort_format_bytes;
+  t.sl_padded = s.sl_padded, t.sl_pos_bytes = s.sl_pos_bytes, t.sl_desc_n = s.sl_desc_n;
+  t.xd_runs_n = s.xd_runs_n, t.xd_entries = s.xd_entries, t.blocks = s.plan.blocks;
+  t.groups = s.plan.kernel == kCsr3 ? (int64_t)s.h_tasks.size() - 1 : (s.A.m + 63) / 64;
+  t.n_cplanes = s.A.n_cplanes, t.n_slabs = s.n_slabs;
+  return t;
+}
+
+// The views of each table family that a launch reads, into s.dp.
+static void use_dict(Shard &s) {
+  s.dp.xd_blk = s.d_xd_blk;
+  s.dp.xd_runs = s.d_xd_runs;
+  s.dp.xd_lds_bytes = s.xd_lds_bytes;
+}
+
+// Row slices: the launch reads the slice-major streams, one length per row
+// and one descriptor per task instead of the CSR-order streams and the row
+// pointers; the CSR-order values of an owned matrix are released (nothing
+// this handle launches reads them; a borrowed one has no d_val).
+static void use_slices(Shard &s) {
+  s.dp.sl_desc = s.d_sl_desc;
+  s.dp.sl_len = s.d_sl_len;
+  s.dp.sl_pos = s.d_sl_pos;
+  s.dp.sl_ppre = s.d_sl_ppre;
+  s.dp.sl_pos_bits = s.sl_pos_bits;
+  s.dp.sl_val = s.d_sl_val;
+  s.dp.n_slices = (int32_t)s.sl_desc_n;
+  s.plan.row_slices = true;
+  if (s.d_val) {
+    s.dev.release(s.d_val);
+    s.d_val = nullptr;
+    s.A.val = nullptr;
+  }
+}
+
+static void use_slabs(Shard &s) {
+  s.dp.n_slabs = s.n_slabs;
+  s.dp.slab_rp = s.d_slab_rp;
+  s.dp.slab_col = s.d_slab_col;
+  s.dp.slab_val = s.d_slab_val;
+}
+
+// The launch's tables for one planned shard (needs s.plan and s.h_rp): the
+// serial bound, the split rows, which of the tables build_row_tables made
+// this launch shape can read (the others fall back to the 32-bit columns),
+// and the device copies of the x windows and the wave tasks.
+int build_plan_tables(Shard &s, unsigned flags) {
+  const int kern = s.plan.kernel;
+  const bool tasks = kern == kCsr3 && !s.h_tasks.empty();
+  const bool serial = s.tune.deterministic == HSPMV_DETERMINISTIC_SERIAL;  // every row by one lane, in order
+  int rc;
+  s.dp = DevPlan();
+  s.dp.serial_max = s.dtype == HSPMV_F32 ? kSerialMaxF32 : kSerialMax;  // by the vectors' dtype
+  if (serial && kern != kStream && kern != kCsr3)
+    return set_error(HSPMV_E_INVALID, "deterministic = 3 (serial order) needs the row kernels, and "
+                                      "they cannot address this matrix (32-bit offsets)");
+  if (serial) s.dp.serial_max = INT32_MAX;
+  else if (s.tune.serial_max > 0) s.dp.serial_max = s.tune.serial_max;  // A/B knob (HSPMV_SERIAL_MAX, diagnostic builds)
+  if (kern == kCsort) {  // long rows are slices of the csort blocks
     s.dp.cs = s.csort;
     s.plan.blocks = s.csort.n_wg;
     s.plan.u = s.csort.u;
-    const double alg = alg_bytes_of(s.A.m, s.x_entries, s.A.nnz, dtype, s.val_dtype, 0, 0);
-    s.c16_saved = alg - s.csort_format_bytes;
+    s.c16_saved = c16_saved_of(kFmtCsort, saved_terms(s, 0));
     return HSPMV_OK;
   }
-  if (s.plan.kernel != kVector && !(flags & HSPMV_FLAG_NO_SPLIT)) {
-    std::vector<int32_t> lrow, lcs(1, 0), ck;
-    for (int64_t r = 0; r < m; ++r) {
-      const int32_t b = rp[r], e = rp[r + 1];
-      if (e - b <= kLongRow) continue;
-      long_nnz += e - b;
-      lrow.push_back((int32_t)r);
-      for (int32_t k = b; k < e; k += kLongChunk) {
-        ck.push_back(k);
-        ck.push_back(e - k > kLongChunk ? k + kLongChunk : e);
-      }
-      lcs.push_back((int32_t)(ck.size() / 2));
-    }
-    if (!lrow.empty() && s.dp.serial_max == INT32_MAX) {  // serial order: one workgroup per row
-      int rc;
-      const int64_t nl = (int64_t)lrow.size();
-      if ((rc = s.dev.upload(&s.d_long_row, lrow.data(), 4 * lrow.size()))) return rc;
-      if ((rc = s.dev.alloc(&s.d_partials, dtype_size(dtype) * (size_t)nl))) return rc;
-      s.dp.partials = s.d_partials;  // the rows' sums, scattered into y after the row kernel
-      s.dp.long_t = kLongRow;
-      s.dp.n_long = (int32_t)nl;
-      s.dp.long_row = s.d_long_row;
-      s.dp.long_serial = true;
-      if ((rc = s.dev.new_stream(&s.dp.long_stream)) || (rc = s.dev.new_event(&s.dp.long_fork)) ||
-          (rc = s.dev.new_event(&s.dp.long_join)))
-        return rc;
-    } else if (!lrow.empty()) {
-      int rc;
-      const int64_t nl = (int64_t)lrow.size(), nc = (int64_t)ck.size() / 2;
-      if ((rc = s.dev.upload(&s.d_long_row, lrow.data(), 4 * lrow.size()))) return rc;
-      if ((rc = s.dev.upload(&s.d_long_cstart, lcs.data(), 4 * lcs.size()))) return rc;
-      if ((rc = s.dev.upload(&s.d_chunk_k, ck.data(), 4 * ck.size()))) return rc;
-      if ((rc = s.dev.alloc(&s.d_partials, dtype_size(dtype) * (size_t)nc))) return rc;
-      s.dp.long_t = kLongRow;
-      s.dp.n_long = (int32_t)nl;
-      s.dp.n_chunks = (int32_t)nc;
-      s.dp.long_row = s.d_long_row;
-      s.dp.long_cstart = s.d_long_cstart;
-      s.dp.chunk_k = s.d_chunk_k;
-      s.dp.partials = s.d_partials;
-    }
-  }
-  if (s.plan.kernel == kVector) {
-    s.A.col16 = nullptr;  // the vector kernel reads 32-bit columns
+  SplitPlan L;
+  if (kern != kVector && plan_split_rows(s.h_rp.data(), s.A.m, flags, L) && (rc = upload_split_rows(s, L)))
+    return rc;
+  int format = kFmtCol32;
+  if (kern == kVector) {  // the vector kernel reads 32-bit columns
+    s.A.col16 = nullptr;
     s.A.cbase = nullptr;
     s.A.cplanes = nullptr;
     s.A.n_cplanes = 0;
   }
   if (s.xd_shape) {
-    const bool fits = (s.xd_shape == kStream && s.plan.kernel == kStream && s.plan.groups == 1 &&
+    const bool fits = (s.xd_shape == kStream && kern == kStream && s.plan.groups == 1 &&
                        s.plan.waves_per_block == 4) ||
-                      (s.xd_shape == kCsr3 && s.plan.kernel == kCsr3 && !s.h_tasks.empty() &&
-                       s.plan.waves_per_block == s.A.task_waves);
-    const double sv = (double)dtype_size(dtype), sval = (double)dtype_size(s.val_dtype);
-    if (fits && s.d_sl_desc) {
-      // row slices: the launch reads the slice-major streams, one length per
-      // row and one descriptor per task instead of the CSR-order streams and
-      // the row pointers; the CSR-order values of an owned matrix are released
-      // (nothing this handle launches reads them; a borrowed one has no d_val)
-      s.dp.xd_blk = s.d_xd_blk;
-      s.dp.xd_runs = s.d_xd_runs;
-      s.dp.xd_lds_bytes = s.xd_lds_bytes;
-      s.dp.sl_desc = s.d_sl_desc;
-      s.dp.sl_len = s.d_sl_len;
-      s.dp.sl_pos = s.d_sl_pos;
-      s.dp.sl_ppre = s.d_sl_ppre;
-      s.dp.sl_pos_bits = s.sl_pos_bits;
-      s.dp.sl_val = s.d_sl_val;
-      s.dp.n_slices = (int32_t)s.sl_desc_n;
-      s.plan.row_slices = true;
-      if (s.d_val) {
-        s.dev.release(s.d_val);
-        s.d_val = nullptr;
-        s.A.val = nullptr;
-      }
-      s.c16_saved = (double)s.A.nnz * (sval + 4.0) + 4.0 * (double)(m + 1) -
-                    (64.0 * (double)s.sl_padded * sval + (double)s.sl_pos_bytes + (double)m +
-                     8.0 * (double)(s.sl_desc_n + 1)) -
-                    4.0 * (double)(s.xd_runs_n * 2) - 4.0 * (double)s.plan.blocks -
-                    sv * (double)(s.xd_entries - s.x_entries);
-    } else if (fits) {
-      s.dp.xd_blk = s.d_xd_blk;
-      s.dp.xd_runs = s.d_xd_runs;
-      s.dp.xd_lds_bytes = s.xd_lds_bytes;
-      // index bytes: 2 instead of 4 per in-kernel nonzero, plus the tables;
-      // x: the staged entries instead of the distinct columns
-      s.c16_saved = 2.0 * (double)(s.A.nnz - long_nnz) - 4.0 * (double)(s.xd_runs_n * 2) -
-                    4.0 * (double)s.plan.blocks - sv * (double)(s.xd_entries - s.x_entries);
-    } else {  // planned for another block shape: the kernels read the 32-bit columns
+                      (s.xd_shape == kCsr3 && tasks && s.plan.waves_per_block == s.A.task_waves);
+    if (fits) use_dict(s);
+    if (fits && s.d_sl_desc) use_slices(s);
+    if (!fits) {  // planned for another block shape: the kernels read the 32-bit columns
       s.A.col16 = nullptr;
       drop_slices(s);
     }
-  } else if (s.A.col16 && s.A.c16_mode == 2 &&
-             (s.plan.kernel != s.c16g_shape || (s.plan.kernel == kCsr3 && s.h_tasks.empty()))) {
+    format = !fits ? kFmtCol32 : s.d_sl_desc ? kFmtSlices : kFmtDict;
+  } else if (s.A.col16 && s.A.c16_mode == 2 && (kern != s.c16g_shape || (kern == kCsr3 && !tasks))) {
     s.A.col16 = nullptr;  // group bases built for another row grouping: 32-bit columns
     s.A.cbase = nullptr;
-  } else if (s.A.col16 && s.A.c16_mode == 2) {
-    const int64_t ngb = s.plan.kernel == kCsr3 ? (int64_t)s.h_tasks.size() - 1 : (s.A.m + 63) / 64;
-    s.c16_saved = 2.0 * (double)(s.A.nnz - long_nnz) - 4.0 * (double)ngb;
   } else if (s.A.col16) {
-    const int64_t nb = (s.A.nnz + (int64_t(1) << kC16Shift) - 1) >> kC16Shift;
-    s.c16_saved = 2.0 * (double)(s.A.nnz - long_nnz) - 4.0 * (double)nb -
-                  (double)s.A.n_cplanes * (double)(s.A.nnz - long_nnz) / 8.0;
+    format = s.A.c16_mode == 2 ? kFmtGroup16 : kFmtBlock16;
   }
-  if (s.n_slabs && (s.plan.kernel == kStream || s.plan.kernel == kCsr3)) {
-    s.dp.n_slabs = s.n_slabs;
-    s.dp.slab_rp = s.d_slab_rp;
-    s.dp.slab_col = s.d_slab_col;
-    s.dp.slab_val = s.d_slab_val;
-    // per extra pass: one more row-pointer array, and y read back + rewritten
-    const double sv = (double)dtype_size(dtype);
-    s.c16_saved = -(double)(s.n_slabs - 1) * (4.0 * (double)(m + 1) + 2.0 * sv * (double)m);
+  if (s.n_slabs && (kern == kStream || kern == kCsr3)) {
+    use_slabs(s);
+    format = kFmtSlabs;
   }
-  const std::vector<int32_t> &xw = s.plan.kernel == kStream ? s.h_xwin : s.h_xwin_t;
-  if ((s.plan.kernel == kStream || (s.plan.kernel == kCsr3 && !s.h_tasks.empty())) && !xw.empty()) {
-    int rc;
+  if (format != kFmtCol32) s.c16_saved = c16_saved_of(format, saved_terms(s, L.long_nnz));
+  const std::vector<int32_t> &xw = kern == kStream ? s.h_xwin : s.h_xwin_t;
+  if ((kern == kStream || tasks) && !xw.empty()) {
     if ((rc = s.dev.upload(&s.d_xwin, xw.data(), 4 * xw.size()))) return rc;
     s.dp.xwin = s.d_xwin;
   }
   std::vector<int32_t>().swap(s.h_xwin);
   std::vector<int32_t>().swap(s.h_xwin_t);
-  if (s.plan.kernel == kCsr3 && !s.h_tasks.empty()) {
-    int rc;
+  if (tasks) {
     if ((rc = s.dev.upload(&s.d_task, s.h_tasks.data(), 4 * s.h_tasks.size()))) return rc;
     s.dp.task_start = s.d_task;
     s.dp.n_tasks = (int32_t)(s.h_tasks.size() - 1);

@@ -15,7 +15,7 @@ namespace hspmv {
 //               and the serial long-row kernels read.  A row-slice shard has
 //               released it, a borrowed one never had it (A.val is the caller's);
 //   row slices  d_sl_val, slice-major (build_slices);
-//   x slabs     d_slab_val, slab-major (build_xslabs); split rows stay in A.val;
+//   x slabs     d_slab_val, slab-major (plan_xslabs); split rows stay in A.val;
 //   column-sorted  the entry stream (csort.ent / csort.val), sorted by column
 //               inside each workgroup and, under fixed-point slots, scaled per
 //               row by 2^rexp, which follows the values (build_csort).  Only a

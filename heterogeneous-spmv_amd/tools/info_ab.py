@@ -31,6 +31,7 @@ from hspmv import _lib, gen  # noqa: E402
 from hspmv.api import _KERNELS, dtype_code  # noqa: E402
 from ab import load  # noqa: E402
 from test_csort import _hub_rows as csort_hub_rows, _long_rows as csort_long_rows  # noqa: E402
+from test_gpu_parity import _band_random  # noqa: E402
 from test_serial import long_rows  # noqa: E402
 from test_slice_pos12 import OFF, ON, block_run, ragged_all_widths  # noqa: E402
 from test_spmm import long_matrix  # noqa: E402
@@ -115,6 +116,12 @@ def families():
     yield "col16_blocks", lambda L: S(L, band, kernel="stream", flags=_lib.FLAG_COL16,
                                       options={"x_dict": -1, "col16_group": -1})
     yield "col16_groups", lambda L: S(L, band, kernel="stream", options={"col16_group": 1, "x_dict": -1})
+    # block bases with one high-bit plane (random columns within +-50 000 of
+    # the diagonal), and group bases over the packed CSR3 tasks
+    yield "col16_blocks_plane", lambda L: S(L, _band_random(150000, 10, 50000, 6), kernel="stream",
+                                            flags=_lib.FLAG_COL16, options={"x_dict": -1, "col16_group": -1})
+    yield "col16_groups_csr3", lambda L: S(L, st20, hspmv.build_csr3_maps(st20, 20, 10), kernel="csr3",
+                                           options={"col16_group": 1, "x_dict": -1})
     band64 = gen.banded(5000, per_row=10, half=32, seed=5)
     yield "x_windows", lambda L: S(L, band64, kernel="stream", options=no_dict)
     yield "x_dict_stream", lambda L: S(L, st21, kernel="stream", options=OFF)
