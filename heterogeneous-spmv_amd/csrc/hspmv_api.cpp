@@ -52,12 +52,12 @@ int create_single(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *
     // into the views only, never into s.dev.
     HIP_TRY(hipSetDevice(device));
     std::vector<int32_t> cols;  // host copy until the row tables are built
-    if ((rc = read_device_csr(A, s.h_rp, cols))) return rc;
+    if ((rc = read_device_csr(A, s.host.rp, cols))) return rc;
     s.A.m = (int32_t)A->m; s.A.n = A->n; s.A.nnz = A->nnz;
     s.A.row_ptr = A->row_ptr; s.A.col_idx = A->col_idx; s.A.val = A->val;
     s.x_entries = count_distinct_cols(cols.data(), A->nnz, A->n);
     if (maps && maps->n_ssr > 0) {
-      std::vector<int32_t> &o = s.h_outer, &in = s.h_inner;
+      std::vector<int32_t> &o = s.host.outer, &in = s.host.inner;
       o.resize((size_t)(maps->n_ssr + 1));
       in.resize((size_t)(maps->n_sr + 1));
       HIP_TRY(hipMemcpy(o.data(), maps->outer, 4 * o.size(), hipMemcpyDeviceToHost));
@@ -72,7 +72,7 @@ int create_single(hspmv_handle **hp, const hspmv_csr *A, const hspmv_csr3_maps *
     // the values come back to the host too: the x slabs copy them slab-major
     std::vector<char> vals(dtype_size(A->dtype) * (size_t)A->nnz);
     if (A->nnz) HIP_TRY(hipMemcpy(vals.data(), A->val, vals.size(), hipMemcpyDeviceToHost));
-    if ((rc = build_row_tables(s, s.h_rp.data(), cols.data(), vals.data(), A->m, A->n, flags))) return rc;
+    if ((rc = build_row_tables(s, s.host.rp.data(), cols.data(), vals.data(), A->m, A->n, flags))) return rc;
     std::vector<char>().swap(vals);
     std::vector<int32_t>().swap(cols);
     const size_t sv = dtype_size(vec_dtype);
@@ -95,7 +95,7 @@ bool shard_alternates(const hspmv_handle *h, const Shard &s) {
   if (h->sweep_mode == HSPMV_SWEEP_FORWARD || s.A.m == 0) return false;
   if (s.plan.kernel != kStream && s.plan.kernel != kCsr3) return false;
   if (h->sweep_mode == HSPMV_SWEEP_ALTERNATE) return true;
-  return s.dp.n_slabs == 0 && !mall_resident(s.A.m, h->n, s.A.nnz, h->dtype, h->val_dtype);
+  return s.dp.slabs.n == 0 && !mall_resident(s.A.m, h->n, s.A.nnz, h->dtype, h->val_dtype);
 }
 
 // The direction of the next SpMV on s; the caller flips h->sweep_phase once
@@ -503,20 +503,20 @@ static int fill_info(hspmv_handle *h, hspmv_info *out) {
   out->flops = 2.0 * (double)h->nnz;
   for (auto &sh : h->shards) out->device_bytes += sh.dev.bytes();
   out->chunk_u = s.plan.u;
-  out->n_split_rows = s.dp.n_long;
+  out->n_split_rows = s.dp.split.n_long;
   out->xcd_remap = s.plan.xcd_chunk;
   out->groups_per_wave = s.plan.kernel == kStream ? s.plan.groups : 1;
   out->format_bytes = out->alg_bytes;
   for (auto &sh : h->shards) out->format_bytes -= sh.c16_saved;
   out->col16 = s.A.col16 ? 1 + s.A.n_cplanes : 0;
-  out->wave_tasks = s.plan.kernel == kCsr3 ? s.dp.n_tasks : 0;
+  out->wave_tasks = s.plan.kernel == kCsr3 ? s.dp.tasks.n : 0;
   out->x_windows = s.dp.xwin ? 1 : 0;
-  out->x_dict = s.dp.xd_blk ? 1 : 0;
-  out->x_slabs = s.dp.n_slabs;
+  out->x_dict = s.dp.xd.blk ? 1 : 0;
+  out->x_slabs = s.dp.slabs.n;
   out->col16_group = (s.A.col16 && s.A.c16_mode == 2) ? 1 : 0;
   out->csort_parts = s.plan.kernel == kCsort ? s.dp.cs.H : 0;
   out->n_split_rows = s.plan.kernel == kCsort ? s.dp.cs.n_long : out->n_split_rows;
-  for (auto &sh : h->shards) out->x_dict_entries += sh.dp.xd_blk ? sh.xd_entries : 0;
+  for (auto &sh : h->shards) out->x_dict_entries += sh.dp.xd.blk ? sh.saved.xd_entries : 0;
   out->placement_trials = (int32_t)s.place_us.size();
   out->placement_pick = s.place_pick;
   for (size_t k = 0; k < s.place_us.size() && k < 8; ++k) out->placement_us[k] = s.place_us[k];
@@ -537,8 +537,8 @@ static int fill_info(hspmv_handle *h, hspmv_info *out) {
   out->csort_fixed_point = s.plan.kernel == kCsort && s.dp.cs.fixed ? 1 : 0;
   out->serial_order = 1;
   for (auto &sh : h->shards) out->serial_order &= sh.dp.serial_max == INT32_MAX ? 1 : 0;
-  out->row_slices = s.dp.sl_desc ? 1 : 0;
-  out->slice_pos_bits = s.dp.sl_desc ? s.dp.sl_pos_bits : 0;
+  out->row_slices = s.dp.sl.desc ? 1 : 0;
+  out->slice_pos_bits = s.dp.sl.pos_bits;
   out->sweep = shard_alternates(h, s) ? 1 : 0;
   if (s.plan.kernel == kCsort)
     for (int hh = 0; hh < 4; ++hh) out->csort_part_begin[hh] = s.csort_part_begin[hh];

@@ -724,7 +724,7 @@ bool plan_csort(const int32_t *rp, const int32_t *col, const void *val, int64_t 
 int upload_csort(Shard &s, const CsortPlan &P) {
   int rc;
   // the tables go straight into the launch description (s.dev owns them)
-  DevCsort &c = s.csort;
+  DevCsort &c = s.built.cs;
   c = DevCsort();
   auto up = [&](auto **d, const auto &h) -> int {
     using E = typename std::decay_t<decltype(h)>::value_type;
@@ -774,7 +774,7 @@ int upload_csort(Shard &s, const CsortPlan &P) {
   s.csort_seg_chunks = P.seg_chunks;
   s.csort_wg_stats = P.wg_stats;
   for (int h = 0; h < 4; ++h) s.csort_part_begin[h] = P.part_begin[h];
-  s.csort_format_bytes = P.format_bytes + (double)s.x_entries * (double)dtype_size(P.dtype);
+  s.saved.csort_format_bytes = P.format_bytes + (double)s.x_entries * (double)dtype_size(P.dtype);
   s.A.has_csort = true;
   return HSPMV_OK;
 }

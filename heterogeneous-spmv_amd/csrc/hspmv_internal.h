@@ -36,7 +36,7 @@ struct DevCSR {
   // dictionaries were built for this shard
   bool has_xwin = false, has_xdict = false;
   bool has_xdict_tasks = false;  // x dictionaries built for packed CSR3 tasks
-  bool has_slices = false;       // ... and stored as row slices (DevPlan.sl_desc)
+  bool has_slices = false;       // ... and stored as row slices (DevPlan.sl)
   int32_t n_slabs = 1;        // x slabs: the row kernel's passes (each sees ~nnz / n_slabs)
   int32_t task_waves = 4;     // CSR3 wave tasks per workgroup: 4 (8 with 8-task dictionary
                               // blocks); the SSR plan: ssr_waves() per super-super-row
@@ -262,21 +262,23 @@ struct DevCsort {
 };
 constexpr uint32_t kCsortSrcPad = 0xFFFFFFFFu;
 
-// Device-side tables the host planner builds once per shard (all optional).
-struct DevPlan {
-  // CSR-3: wave task t covers rows [task_start[t], task_start[t+1]);
-  // either super-rows packed into <= 64-row tasks (default), or
-  // waves_per_block tasks per super-super-row, nnz-balanced on super-row
-  // boundaries (HSPMV_CSR3_PLAN=ssr).
-  const int32_t *task_start = nullptr;
-  int32_t n_tasks = 0;
+// Device-side tables the host planner builds once per shard (all optional),
+// one record per table family: the upload that builds a family fills its
+// record, and a launch reads the records build_plan_tables selected.
+// CSR-3: wave task t covers rows [start[t], start[t+1]); either super-rows
+// packed into <= 64-row tasks (default), or waves_per_block tasks per
+// super-super-row, nnz-balanced on super-row boundaries (HSPMV_CSR3_PLAN=ssr).
+struct DevTasks {
+  const int32_t *start = nullptr;
+  int32_t n = 0;
   // 1: a task's 64-row groups end on multiples of 64 (its first group may be
   // shorter) -- the SSR plan's aligned cut (ssr_tasks_aligned); 0: groups of
   // 64 rows from the task's first row
-  int32_t task_align = 0;
-  // split rows
+  int32_t align = 0;
+};
+// split rows
+struct DevSplit {
   int32_t long_t = 0x7fffffff;  // rows with more nonzeros are split rows
-  int32_t serial_max = kSerialMax;  // rows up to this length are summed serially (fp32: kSerialMaxF32)
   int32_t n_long = 0, n_chunks = 0;
   bool long_serial = false;  // split rows summed in order by hspmv_long_serial (deterministic = 3)
   // ... on a stream of their own, forked from and joined back into the
@@ -287,43 +289,57 @@ struct DevPlan {
   const int32_t *long_cstart = nullptr; // n_long+1, chunk ranges per split row
   const int32_t *chunk_k = nullptr;     // 2*n_chunks: [k0, k1) per chunk
   void *partials = nullptr;             // n_chunks partial sums (dtype)
+};
+// Block x dictionaries (STREAM with one group per wave: 256-row blocks;
+// CSR3: blocks of four packed tasks): blk[b], blk[b+1] bound block b's
+// {x_start, lds_off} run records in runs (int2), the last a sentinel
+// {0, entries}; col16 then holds each nonzero's position in the staged xs.
+// lds_bytes = the largest block's dictionary (dynamic LDS per block).
+struct DevXdict {
+  const int32_t *blk = nullptr;
+  const void *runs = nullptr;
+  int32_t lds_bytes = 0;
+};
+// Row slices (hspmv_slices.cpp): the dictionary handle's matrix stored per
+// 64-row wave task column-major, one lane per row (hspmv_slices,
+// slice_kernel.cuh).  desc: {prefix, first row} per task and a closing pair
+// ({padded slot columns, m}); slice t's values start at val + 64 * prefix
+// elements; len: one length per row.  Positions: pos_bits = 16, slice t's
+// start at pos + 64 * prefix; 12, the packed stream, slice t's at
+// 128 * ppre[t] bytes.  DevPlan.sl is set only when the launch runs the slice
+// kernel.
+struct DevSlices {
+  const int32_t *desc = nullptr;
+  const uint8_t *len = nullptr;
+  const uint16_t *pos = nullptr;
+  const int32_t *ppre = nullptr;
+  int32_t pos_bits = 0;
+  void *val = nullptr;  // (the value refresh writes it, refresh.hip)
+  int32_t n = 0;  // descriptors (= wave tasks, the empty ones included)
+};
+// x slabs (irregular gathers, x larger than an XCD's L2): the columns are
+// cut into n equal ranges and the row kernel runs once per slab over a
+// slab-major copy of the matrix -- pass b reads rows
+// [rp[b*(m+1) + r], rp[b*(m+1) + r + 1]) of col / val, so its gathers stay
+// inside one L2-sized slice of x.  Split rows have empty slab segments (the
+// split-row kernels sum them from the CSR).
+struct DevSlabs {
+  int32_t n = 0;
+  const int32_t *rp = nullptr;
+  const int32_t *col = nullptr;
+  void *val = nullptr;  // (the value refresh writes it, refresh.hip)
+};
+struct DevPlan {
+  DevTasks tasks;
+  DevSplit split;
+  int32_t serial_max = kSerialMax;  // rows up to this length are summed serially (fp32: kSerialMaxF32)
   // x windows per row group (STREAM: 64-row groups; CSR3: packed tasks):
   // {lo, w} (int32), w = 0 when the group's columns span more than kXWin
   // entries (then it gathers from global x)
   const void *xwin = nullptr;
-  // Block x dictionaries (STREAM with one group per wave: 256-row blocks;
-  // CSR3: blocks of four packed tasks): xd_blk[b], xd_blk[b+1] bound block
-  // b's {x_start, lds_off} run records in xd_runs (int2), the last a sentinel
-  // {0, entries}; col16 then holds each nonzero's position in the staged xs.
-  // xd_lds_bytes = the largest block's dictionary (dynamic LDS per block).
-  const int32_t *xd_blk = nullptr;
-  const void *xd_runs = nullptr;
-  int32_t xd_lds_bytes = 0;
-  // Row slices (hspmv_slices.cpp): the dictionary handle's matrix stored per
-  // 64-row wave task column-major, one lane per row (hspmv_slices,
-  // slice_kernel.cuh).  sl_desc: {prefix, first row} per task and a closing
-  // pair ({padded slot columns, m}); slice t's values start at sl_val + 64 *
-  // prefix elements; sl_len: one length per row.  Positions: sl_pos_bits =
-  // 16, slice t's start at sl_pos + 64 * prefix; 12, the packed stream, slice
-  // t's at 128 * sl_ppre[t] bytes.  Set only when the launch runs the slice
-  // kernel.
-  const int32_t *sl_desc = nullptr;
-  const uint8_t *sl_len = nullptr;
-  const uint16_t *sl_pos = nullptr;
-  const int32_t *sl_ppre = nullptr;
-  int32_t sl_pos_bits = 0;
-  const void *sl_val = nullptr;
-  int32_t n_slices = 0;  // descriptors (= wave tasks, the empty ones included)
-  // x slabs (irregular gathers, x larger than an XCD's L2): the columns are
-  // cut into n_slabs equal ranges and the row kernel runs
-  // once per slab over a slab-major copy of the matrix -- pass b reads rows
-  // [slab_rp[b*(m+1) + r], slab_rp[b*(m+1) + r + 1]) of slab_col/slab_val,
-  // so its gathers stay inside one L2-sized slice of x.  Split rows have
-  // empty slab segments (the split-row kernels sum them from the CSR).
-  int32_t n_slabs = 0;
-  const int32_t *slab_rp = nullptr;
-  const int32_t *slab_col = nullptr;
-  const void *slab_val = nullptr;
+  DevXdict xd;
+  DevSlices sl;
+  DevSlabs slabs;
   DevCsort cs;  // kCsort
 };
 
@@ -367,7 +383,7 @@ hipError_t launch_rows_f32(const DevCSR &A, const DevPlan &dp, const LaunchPlan 
                            const float *x, float *y, hipStream_t st);
 hipError_t launch_rows_f64(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
                            const double *x, double *y, hipStream_t st);
-// ... of a mixed handle: A.val / dp.sl_val / dp.slab_val hold float
+// ... of a mixed handle: A.val / dp.sl.val / dp.slabs.val hold float
 // (stream_f32v64.hip)
 hipError_t launch_rows_f32v64(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
                               const double *x, double *y, hipStream_t st);
@@ -388,11 +404,11 @@ hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, int val_dt
 // the derived copies of the values rebuilt on the device from src, the new
 // values in the shard's CSR order (val_dtype: the stored values').  Both
 // enqueue one kernel on st, or nothing for an empty table.
-// The row slices' value stream dst (DevPlan.sl_val) of n_slices descriptors
+// The row slices' value stream dst (DevSlices.val) of n_slices descriptors
 // desc with the row lengths len; row_ptr: the shard's CSR row pointers.
 hipError_t launch_refresh_slices(int val_dtype, int64_t n_slices, const int32_t *desc, const uint8_t *len,
                                  const int32_t *row_ptr, const void *src, void *dst, hipStream_t st);
-// The x slabs' slab-major values dst (DevPlan.slab_val) of the n_slabs
+// The x slabs' slab-major values dst (DevSlabs.val) of the n_slabs
 // row-pointer arrays slab_rp, m + 1 entries each.
 hipError_t launch_refresh_slabs(int val_dtype, int32_t m, int64_t nnz, int32_t n_slabs, const int32_t *row_ptr,
                                 const int32_t *slab_rp, const void *src, void *dst, hipStream_t st);

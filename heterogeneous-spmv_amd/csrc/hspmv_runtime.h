@@ -14,7 +14,9 @@
 //                          -> SplitPlan; median_serial_len, wants_csort,
 //                          c16_saved_of over SavedTerms), their uploads
 //                          (upload_col16, upload_xslabs, upload_split_rows) and
-//                          the two sequences build_row_tables / build_plan_tables
+//                          the two sequences build_row_tables (fills the
+//                          records of Shard::built) / build_plan_tables
+//                          (selects the ones the launch reads into Shard::dp)
 //   hspmv_xdict.cpp        block x dictionaries (+ hspmv_xdict_plan), the
 //                          plan entry points' shared preamble (plan_shape)
 //   hspmv_slices.cpp       row slices of dictionary handles (+ hspmv_slices_plan)
@@ -55,9 +57,10 @@ namespace hspmv {
 // The owner of one device's side of a shard or an SpMM operator.  The
 // ownership rule of the whole runtime: what a DevCtx allocated or created it
 // frees -- early through release(), else in its destructor -- and nothing
-// else is ever freed.  Every other device pointer (Shard::d_*, DevCSR,
-// DevPlan, DevCsort, DevMM) is a view: into one of these allocations, or a
-// caller's borrowed array, which never enters a context.
+// else is ever freed.  Every other device pointer (Shard::d_*, the matrix
+// arrays; DevCSR; the table records of Shard::built and Shard::dp, DevCsort
+// among them; DevMM) is a view: into one of these allocations, or a caller's
+// borrowed array, which never enters a context.
 // alloc / upload / open / new_* expect `device` to be the current device.
 struct DevCtx {
   int device = 0;
@@ -114,6 +117,30 @@ struct DevCtx {
   int upload_raw(void **p, const void *src, size_t bytes);
 };
 
+// What a launch reads instead of the 32-bit CSR streams, and the numbers the
+// bytes it saves are worked out from (c16_saved_of: Shard::c16_saved).
+enum SavedFormat { kFmtCol32 = 0, kFmtCsort, kFmtSlices, kFmtDict, kFmtGroup16, kFmtBlock16, kFmtSlabs };
+struct SavedTerms {
+  int dtype = HSPMV_F64, val_dtype = HSPMV_F64;
+  int64_t m = 0, nnz = 0, long_nnz = 0, x_entries = 0;
+  double csort_format_bytes = 0.0;                      // kFmtCsort
+  int64_t sl_padded = 0, sl_pos_bytes = 0, sl_desc_n = 0;  // kFmtSlices
+  int64_t xd_runs_n = 0, xd_entries = 0, blocks = 0;    // kFmtSlices, kFmtDict
+  int64_t groups = 0;                                   // kFmtGroup16: the bases read
+  int n_cplanes = 0, n_slabs = 0;                       // kFmtBlock16; kFmtSlabs
+};
+
+// The host copies a shard is planned from.  upload_shard (a borrowed matrix:
+// create_single) fills rp, outer and inner; build_row_tables the wave tasks
+// (build_xdict may cut them) and the x windows, which it empties again when
+// another table is taken.  build_plan_tables reads them last: finish_shard
+// releases the whole record once that has returned.
+struct HostTables {
+  std::vector<int32_t> rp, outer, inner;  // row pointers and CSR-3 maps, rebased to the shard
+  std::vector<int32_t> tasks;             // CSR-3 wave tasks (build_tasks)
+  std::vector<int32_t> xwin, xwin_t;      // x windows per 64-row group / per packed CSR-3 task
+};
+
 // One row-range shard on one GPU: views, host tables and the plan; dev owns
 // the device side.
 struct Shard {
@@ -127,43 +154,28 @@ struct Shard {
   DevCSR A;          // device view (rows rebased to 0)
   LaunchPlan plan;
   double mean_rows_per_ssr = 0.0;
-  // views of dev's allocations, carried from build_row_tables to build_plan_tables
+  // views of dev's allocations: the matrix arrays, and the 16-bit column trio
+  // (writable slots: the placement trials repoint them)
   int32_t *d_rp = nullptr, *d_ci = nullptr, *d_outer = nullptr, *d_inner = nullptr;
   uint16_t *d_c16 = nullptr;  // 16-bit column offsets
   int32_t *d_cbase = nullptr;
   uint64_t *d_cplanes = nullptr;
-  int32_t *d_xwin = nullptr;         // STREAM x windows {lo, w} per 64-row group
-  int32_t *d_xd_blk = nullptr;       // block x dictionaries (build_xdict)
+  // Every other device table has one record (DevPlan's, hspmv_internal.h),
+  // filled once by the upload_* / build_* that makes the table: into `built`,
+  // what this shard has on the device.  dp is what the launch reads:
+  // build_plan_tables takes a record of `built` whole, or leaves dp's empty
+  // when the planned launch shape cannot read that table.
+  DevPlan built, dp;
   int64_t xd_cut = 0;                // CSR3 dictionary blocks cut in two (split_xd_blocks)
-  int32_t *d_xd_runs = nullptr;
-  int32_t xd_lds_bytes = 0;
   int xd_shape = 0;                  // 0 none, kStream (256-row blocks), kCsr3 (4 packed tasks)
-  int64_t xd_entries = 0;            // x entries staged per SpMV (all blocks)
-  int64_t xd_runs_n = 0;             // run records incl. sentinels
-  // row slices (build_slices): the slice kernel's streams, built with the
-  // dictionaries when the handle is eligible (hspmv_slices.cpp)
-  int32_t *d_sl_desc = nullptr;
-  uint8_t *d_sl_len = nullptr;
-  uint16_t *d_sl_pos = nullptr;   // the position stream: 16-bit, or packed (sl_pos_bits = 12)
-  int32_t *d_sl_ppre = nullptr;   // packed stream only: each slice's start in 128-byte units
-  void *d_sl_val = nullptr;
-  int64_t sl_desc_n = 0, sl_padded = 0;  // descriptors, sum of slice widths
-  int sl_pos_bits = 0;            // 0 no slices, else 12 or 16 (hspmv_slices_pack)
-  int64_t sl_pos_bytes = 0;       // position bytes read per SpMV (the stream and d_sl_ppre)
-  int32_t *d_slab_rp = nullptr;      // x slabs (plan_xslabs): per-slab row pointers,
-  int32_t *d_slab_col = nullptr;     // slab-major columns and values
-  void *d_slab_val = nullptr;
-  int32_t n_slabs = 0;
-  // column-sorted row blocks (build_csort): the launch description of the
-  // tables (copied into dp.cs when the planner picks kCsort)
-  DevCsort csort;
-  double csort_format_bytes = 0.0;   // bytes one csort SpMV moves
+  // The report's numbers (c16_saved_of, hspmv_info): each upload writes its
+  // table's terms, build_plan_tables those of the planned launch.
+  SavedTerms saved;
   int64_t csort_chunks = 0, csort_seg_chunks = 0;  // chunks, and those stored slot-sorted
   std::vector<int64_t> csort_wg_stats;  // diagnostic builds: 8 cost terms per workgroup
   int64_t csort_part_begin[4] = {0, 0, 0, 0};  // first column of each column part
   int c16g_shape = 0;                // group-base columns built for kStream groups / kCsr3 tasks
-  std::vector<int32_t> h_xwin;       // built at upload (host columns at hand)
-  std::vector<int32_t> h_xwin_t;     // the same per packed CSR-3 task
+  HostTables host;
   void *d_val = nullptr;   // own values (none for a borrowed matrix)
   void *d_x = nullptr;     // own x (n entries)
   void *d_y = nullptr;     // own y (m_shard entries) -- or a view into d_yfull
@@ -172,13 +184,6 @@ struct Shard {
   void *y = nullptr;       // y in use (own or bound)
   int64_t x_entries = 0;   // distinct columns of this shard
   double c16_saved = 0.0;  // bytes per SpMV the 16-bit column offsets save
-  // planner tables: CSR-3 wave tasks and split-row chunks
-  DevPlan dp;
-  int32_t *d_task = nullptr, *d_long_row = nullptr, *d_long_cstart = nullptr,
-          *d_chunk_k = nullptr;
-  void *d_partials = nullptr;
-  // host copies kept until the plan is built
-  std::vector<int32_t> h_rp, h_outer, h_inner, h_tasks;
   // placement trials (place_shard): SpMV time of each array set, the kept one
   std::vector<double> place_us;
   int place_pick = 0;
@@ -263,8 +268,9 @@ bool irregular_gathers(const int32_t *rp, const int32_t *col, int64_t m, double 
 // the plan_* functions make no HIP call and touch no Shard, fill a plain
 // struct and return whether the table is taken (dtype: the vectors',
 // val_dtype: the stored values'); the upload_* functions hold the uploads and
-// allocations and set the Shard / DevCSR / DevPlan fields that describe the
-// table, nothing else.  A plan is a local that dies once its upload returns.
+// allocations and fill the table's record in Shard::built, its terms in
+// Shard::saved and its DevCSR hints, nothing else.  A plan is a local that
+// dies once its upload returns.
 // tools/row_tables_check.cpp decodes every table back into the matrix
 // (make asan-row-tables; tests/test_row_tables_plan.py).
 //
@@ -305,18 +311,7 @@ int upload_split_rows(Shard &s, const SplitPlan &P);
 int32_t median_serial_len(const int32_t *rp, int64_t m);
 bool wants_csort(const int32_t *rp, const int32_t *col, int64_t m, int64_t n, int dtype, int val_dtype,
                  unsigned flags, const Tuning &tune);
-// What a launch reads instead of the 32-bit CSR streams, and the numbers the
-// bytes it saves are worked out from (c16_saved_of: Shard::c16_saved).
-enum SavedFormat { kFmtCol32 = 0, kFmtCsort, kFmtSlices, kFmtDict, kFmtGroup16, kFmtBlock16, kFmtSlabs };
-struct SavedTerms {
-  int dtype = HSPMV_F64, val_dtype = HSPMV_F64;
-  int64_t m = 0, nnz = 0, long_nnz = 0, x_entries = 0;
-  double csort_format_bytes = 0.0;                      // kFmtCsort
-  int64_t sl_padded = 0, sl_pos_bytes = 0, sl_desc_n = 0;  // kFmtSlices
-  int64_t xd_runs_n = 0, xd_entries = 0, blocks = 0;    // kFmtSlices, kFmtDict
-  int64_t groups = 0;                                   // kFmtGroup16: the bases read
-  int n_cplanes = 0, n_slabs = 0;                       // kFmtBlock16; kFmtSlabs
-};
+// (SavedFormat, SavedTerms: above Shard, which holds the terms)
 double c16_saved_of(int format, const SavedTerms &t);
 // (the vectors' and the values' dtypes: s.dtype, s.val_dtype)
 int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
@@ -426,8 +421,9 @@ struct CsortPlan {
 // matrix (make asan-csort; tests/test_csort_plan.py).
 bool plan_csort(const int32_t *rp, const int32_t *col, const void *val, int64_t m, int64_t n, int dtype,
                 unsigned flags, const Tuning &tune, const CsortLimits &lim, CsortPlan &P);
-// Uploads and allocations only: fills s.csort, the shard's csort_* report
-// fields (format bytes with the x term of s.x_entries) and s.A.has_csort.
+// Uploads and allocations only: fills s.built.cs, the shard's csort_* report
+// fields, s.saved.csort_format_bytes (with the x term of s.x_entries) and
+// s.A.has_csort.
 int upload_csort(Shard &s, const CsortPlan &P);
 // The device's two limits, plan_csort, upload_csort; HSPMV_OK without tables
 // (s.A.has_csort stays false) when the planner declines.

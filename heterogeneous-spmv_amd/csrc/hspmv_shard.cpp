@@ -171,7 +171,7 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
   s.row0 = r0;
   s.nnz0 = k0;
   int rc;
-  std::vector<int32_t> &rp = s.h_rp;
+  std::vector<int32_t> &rp = s.host.rp;
   rp.resize((size_t)(m + 1));
   for (int64_t i = 0; i <= m; ++i) rp[i] = (int32_t)(A->row_ptr[r0 + i] - k0);
   if ((rc = s.dev.upload(&s.d_rp, rp.data(), 4 * (size_t)(m + 1)))) return rc;
@@ -192,7 +192,7 @@ int upload_shard(Shard &s, const hspmv_csr *A, const hspmv_csr3_maps *mp, int64_
     const int64_t nssr = ssr1 - ssr0;
     const int64_t sr0 = mp->outer[ssr0], sr1 = mp->outer[ssr1];
     const int64_t nsr = sr1 - sr0;
-    std::vector<int32_t> &o = s.h_outer, &in = s.h_inner;
+    std::vector<int32_t> &o = s.host.outer, &in = s.host.inner;
     o.resize((size_t)(nssr + 1));
     in.resize((size_t)(nsr + 1));
     for (int64_t i = 0; i <= nssr; ++i) o[i] = (int32_t)(mp->outer[ssr0 + i] - sr0);
@@ -216,13 +216,11 @@ int finish_shard(Shard &s, unsigned flags, void *stream) {
   // 90th percentile doubled C3's waves for a 7-12 % loss, r01_ab_csr3_tasks)
   const double ssr_rows = s.mean_rows_per_ssr;
   s.plan = plan_launch(s.A, s.dtype, s.val_dtype, flags, ssr_rows,
-                       s.h_tasks.empty() ? 0 : (int64_t)s.h_tasks.size() - 1, s.tune);
+                       s.host.tasks.empty() ? 0 : (int64_t)s.host.tasks.size() - 1, s.tune);
   if ((rc = build_plan_tables(s, flags))) return rc;
   s.x = s.d_x;
   s.y = s.d_y;
-  std::vector<int32_t>().swap(s.h_rp);
-  std::vector<int32_t>().swap(s.h_outer);
-  std::vector<int32_t>().swap(s.h_inner);
+  s.host = HostTables();  // every host copy the plan was built from
   return HSPMV_OK;
 }
 
@@ -268,7 +266,7 @@ static constexpr int kPlacementTrials = 0;
 int place_shard(Shard &s, int64_t n) {
   int trials = s.tune.placement_trials > 0 ? std::min(8, s.tune.placement_trials) : kPlacementTrials;
   if (trials <= 1 || (s.plan.kernel != kStream && s.plan.kernel != kCsr3) || s.A.m == 0) return HSPMV_OK;
-  if (s.dp.sl_desc) return HSPMV_OK;  // row slices: the trial sets copy the CSR-order streams
+  if (s.dp.sl.desc) return HSPMV_OK;  // row slices: the trial sets copy the CSR-order streams
   const size_t sv = dtype_size(s.dtype), sval = dtype_size(s.val_dtype);  // x and y; the stored values
   const int64_t m = s.A.m, nnz = s.A.nnz;
   if (mall_resident(m, n, nnz, s.dtype, s.val_dtype)) return HSPMV_OK;  // served from the Infinity Cache: placement does not matter

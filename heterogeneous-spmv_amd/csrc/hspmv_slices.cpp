@@ -205,6 +205,7 @@ static void pack_slice_pos(const int32_t *desc, int64_t nd, const uint16_t *pos,
 }
 
 int upload_slices(Shard &s, const SlicePlan &P) {
+  DevSlices &d = s.built.sl;
   int rc;
   const int64_t nd = (int64_t)P.desc.size() / 2 - 1;
   int32_t bits = 0;
@@ -219,30 +220,26 @@ int upload_slices(Shard &s, const SlicePlan &P) {
       return rc;
     pos_bytes = packed.size();
     table_bytes = 4 * prefix.size();
-    if ((rc = s.dev.upload(&s.d_sl_pos, packed.data(), pos_bytes))) return rc;
-    if ((rc = s.dev.upload(&s.d_sl_ppre, prefix.data(), table_bytes))) return rc;
-  } else if ((rc = s.dev.upload(&s.d_sl_pos, P.pos.data(), pos_bytes))) {  // the plan's stream as it is
+    if ((rc = s.dev.upload(&d.pos, packed.data(), pos_bytes))) return rc;
+    if ((rc = s.dev.upload(&d.ppre, prefix.data(), table_bytes))) return rc;
+  } else if ((rc = s.dev.upload(&d.pos, P.pos.data(), pos_bytes))) {  // the plan's stream as it is
     return rc;
   }
-  if ((rc = s.dev.upload(&s.d_sl_desc, P.desc.data(), 4 * P.desc.size()))) return rc;
-  if ((rc = s.dev.upload(&s.d_sl_len, P.len.data(), P.len.size()))) return rc;
-  if ((rc = s.dev.upload(&s.d_sl_val, P.val.data(), P.val.size()))) return rc;
-  s.sl_desc_n = nd;
-  s.sl_padded = P.padded;
-  s.sl_pos_bits = bits;
-  s.sl_pos_bytes = stream + (int64_t)table_bytes;
+  if ((rc = s.dev.upload(&d.desc, P.desc.data(), 4 * P.desc.size()))) return rc;
+  if ((rc = s.dev.upload(&d.len, P.len.data(), P.len.size()))) return rc;
+  if ((rc = s.dev.upload(&d.val, P.val.data(), P.val.size()))) return rc;
+  d.n = (int32_t)nd;
+  d.pos_bits = bits;
+  s.saved.sl_desc_n = nd;
+  s.saved.sl_padded = P.padded;
+  s.saved.sl_pos_bytes = stream + (int64_t)table_bytes;  // the stream and ppre
   return HSPMV_OK;
 }
 
 void drop_slices(Shard &s) {
-  for (void *p : {(void *)s.d_sl_desc, (void *)s.d_sl_len, (void *)s.d_sl_pos, (void *)s.d_sl_ppre, s.d_sl_val})
-    s.dev.release(p);
-  s.d_sl_desc = nullptr;
-  s.d_sl_len = nullptr;
-  s.d_sl_pos = nullptr;
-  s.d_sl_ppre = nullptr;
-  s.d_sl_val = nullptr;
-  s.sl_pos_bits = 0;
+  const DevSlices &d = s.built.sl;
+  for (const void *p : std::initializer_list<const void *>{d.desc, d.len, d.pos, d.ppre, d.val}) s.dev.release(p);
+  s.built.sl = DevSlices();
   s.A.has_slices = false;
 }
 

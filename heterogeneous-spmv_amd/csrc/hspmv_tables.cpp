@@ -612,11 +612,11 @@ bool plan_xslabs(const int32_t *rp, const int32_t *col, const void *val, int64_t
 
 int upload_xslabs(Shard &s, const XslabPlan &P) {
   int rc;
-  if ((rc = s.dev.upload(&s.d_slab_rp, P.rp.data(), 4 * P.rp.size()))) return rc;
-  if ((rc = s.dev.upload(&s.d_slab_col, P.col.data(), 4 * P.col.size()))) return rc;
-  if ((rc = s.dev.upload(&s.d_slab_val, P.val.data(), P.val.size()))) return rc;
-  s.n_slabs = P.B;
-  s.A.n_slabs = P.B;
+  DevSlabs &d = s.built.slabs;
+  if ((rc = s.dev.upload(&d.rp, P.rp.data(), 4 * P.rp.size()))) return rc;
+  if ((rc = s.dev.upload(&d.col, P.col.data(), 4 * P.col.size()))) return rc;
+  if ((rc = s.dev.upload(&d.val, P.val.data(), P.val.size()))) return rc;
+  d.n = s.saved.n_slabs = s.A.n_slabs = P.B;
   return HSPMV_OK;
 }
 
@@ -694,13 +694,14 @@ bool wants_csort(const int32_t *rp, const int32_t *col, int64_t m, int64_t n, in
 int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void *val, int64_t m,
                      int64_t n, unsigned flags) {
   const int dtype = s.dtype, val_dtype = s.val_dtype;  // the vectors'; the stored values'
+  HostTables &H = s.host;
   s.A.serial_len = median_serial_len(rp, m);
   int waves = 4;
-  build_tasks(rp, m, s.A.n_ssr > 0 ? &s.h_inner : nullptr, s.A.n_ssr > 0 ? &s.h_outer : nullptr,
-              flags, s.tune, s.h_tasks, &waves);
+  build_tasks(rp, m, s.A.n_ssr > 0 ? &H.inner : nullptr, s.A.n_ssr > 0 ? &H.outer : nullptr,
+              flags, s.tune, H.tasks, &waves);
   s.A.task_waves = waves;
-  s.h_xwin.clear();
-  s.h_xwin_t.clear();
+  H.xwin.clear();
+  H.xwin_t.clear();
   int rc;
   if (wants_csort(rp, col, m, n, dtype, val_dtype, flags, s.tune)) {
     if ((rc = build_csort(s, rp, col, val, m, n, dtype, flags))) return rc;
@@ -714,27 +715,27 @@ int build_row_tables(Shard &s, const int32_t *rp, const int32_t *col, const void
     if (plan_xslabs(rp, col, val, m, n, dtype, val_dtype, flags, s.tune, X)) {
       if ((rc = upload_xslabs(s, X))) return rc;
       s.A.col_span_bits = 31;  // slab passes read 32-bit columns from global x
-      if (!s.h_tasks.empty()) slab_kernel_rule(s, rp, m, flags);
+      if (!H.tasks.empty()) slab_kernel_rule(s, rp, m, flags);
       return HSPMV_OK;
     }
   }
-  s.h_xwin = xwin_table(rp, col, m, nullptr, s.tune);
-  if (!s.h_tasks.empty()) s.h_xwin_t = xwin_table(rp, col, m, &s.h_tasks, s.tune);
-  const int kern = kernel_for_tables(s.A.n_ssr, !s.h_tasks.empty(), flags);
-  const bool have_xwin = kern == kCsr3 ? !s.h_xwin_t.empty() : !s.h_xwin.empty();
+  H.xwin = xwin_table(rp, col, m, nullptr, s.tune);
+  if (!H.tasks.empty()) H.xwin_t = xwin_table(rp, col, m, &H.tasks, s.tune);
+  const int kern = kernel_for_tables(s.A.n_ssr, !H.tasks.empty(), flags);
+  const bool have_xwin = kern == kCsr3 ? !H.xwin_t.empty() : !H.xwin.empty();
   if ((rc = build_xdict(s, rp, col, val, m, n, flags, have_xwin))) return rc;
   if (s.xd_shape) {
-    s.h_xwin.clear();
-    s.h_xwin_t.clear();
+    H.xwin.clear();
+    H.xwin_t.clear();
     s.A.col_span_bits = 1;
     s.A.has_xdict = s.xd_shape == kStream;
     s.A.has_xdict_tasks = s.xd_shape == kCsr3;
     return HSPMV_OK;
   }
-  s.A.has_xwin = !s.h_xwin.empty();
+  s.A.has_xwin = !H.xwin.empty();
   Col16Plan C;
   bool c16 = (kern == kStream || kern == kCsr3) &&
-             plan_col16g(rp, col, m, n, dtype, val_dtype, flags, s.tune, kern == kCsr3 ? &s.h_tasks : nullptr, C);
+             plan_col16g(rp, col, m, n, dtype, val_dtype, flags, s.tune, kern == kCsr3 ? &H.tasks : nullptr, C);
   if (!c16) c16 = plan_col16(col, rp[m], m, n, dtype, val_dtype, flags, C);
   if (C.span_bits) s.A.col_span_bits = C.span_bits;
   return c16 ? upload_col16(s, C) : HSPMV_OK;
@@ -767,22 +768,19 @@ bool plan_split_rows(const int32_t *rp, int64_t m, unsigned flags, SplitPlan &P)
 int upload_split_rows(Shard &s, const SplitPlan &P) {
   const bool serial = s.dp.serial_max == INT32_MAX;
   const size_t nl = P.long_row.size(), nc = serial ? 0 : P.chunk_k.size() / 2;
+  DevSplit &d = s.built.split;
   int rc;
-  if ((rc = s.dev.upload(&s.d_long_row, P.long_row.data(), 4 * nl))) return rc;
-  if (!serial && ((rc = s.dev.upload(&s.d_long_cstart, P.long_cs.data(), 4 * P.long_cs.size())) ||
-                  (rc = s.dev.upload(&s.d_chunk_k, P.chunk_k.data(), 4 * P.chunk_k.size()))))
+  if ((rc = s.dev.upload(&d.long_row, P.long_row.data(), 4 * nl))) return rc;
+  if (!serial && ((rc = s.dev.upload(&d.long_cstart, P.long_cs.data(), 4 * P.long_cs.size())) ||
+                  (rc = s.dev.upload(&d.chunk_k, P.chunk_k.data(), 4 * P.chunk_k.size()))))
     return rc;
-  if ((rc = s.dev.alloc(&s.d_partials, dtype_size(s.dtype) * (serial ? nl : nc)))) return rc;
-  s.dp.long_t = P.long_t;
-  s.dp.n_long = (int32_t)nl;
-  s.dp.n_chunks = (int32_t)nc;
-  s.dp.long_row = s.d_long_row;
-  s.dp.long_cstart = s.d_long_cstart;
-  s.dp.chunk_k = s.d_chunk_k;
-  s.dp.partials = s.d_partials;
-  s.dp.long_serial = serial;
-  if (serial && ((rc = s.dev.new_stream(&s.dp.long_stream)) || (rc = s.dev.new_event(&s.dp.long_fork)) ||
-                 (rc = s.dev.new_event(&s.dp.long_join))))
+  if ((rc = s.dev.alloc(&d.partials, dtype_size(s.dtype) * (serial ? nl : nc)))) return rc;
+  d.long_t = P.long_t;
+  d.n_long = (int32_t)nl;
+  d.n_chunks = (int32_t)nc;
+  d.long_serial = serial;
+  if (serial && ((rc = s.dev.new_stream(&d.long_stream)) || (rc = s.dev.new_event(&d.long_fork)) ||
+                 (rc = s.dev.new_event(&d.long_join))))
     return rc;
   return HSPMV_OK;
 }
@@ -819,37 +817,12 @@ double c16_saved_of(int format, const SavedTerms &t) {
   return 0.0;
 }
 
-static SavedTerms saved_terms(const Shard &s, int64_t long_nnz) {
-  SavedTerms t;
-  t.dtype = s.dtype, t.val_dtype = s.val_dtype;
-  t.m = s.A.m, t.nnz = s.A.nnz, t.long_nnz = long_nnz, t.x_entries = s.x_entries;
-  t.csort_format_bytes = s.csort_format_bytes;
-  t.sl_padded = s.sl_padded, t.sl_pos_bytes = s.sl_pos_bytes, t.sl_desc_n = s.sl_desc_n;
-  t.xd_runs_n = s.xd_runs_n, t.xd_entries = s.xd_entries, t.blocks = s.plan.blocks;
-  t.groups = s.plan.kernel == kCsr3 ? (int64_t)s.h_tasks.size() - 1 : (s.A.m + 63) / 64;
-  t.n_cplanes = s.A.n_cplanes, t.n_slabs = s.n_slabs;
-  return t;
-}
-
-// The views of each table family that a launch reads, into s.dp.
-static void use_dict(Shard &s) {
-  s.dp.xd_blk = s.d_xd_blk;
-  s.dp.xd_runs = s.d_xd_runs;
-  s.dp.xd_lds_bytes = s.xd_lds_bytes;
-}
-
 // Row slices: the launch reads the slice-major streams, one length per row
 // and one descriptor per task instead of the CSR-order streams and the row
 // pointers; the CSR-order values of an owned matrix are released (nothing
 // this handle launches reads them; a borrowed one has no d_val).
 static void use_slices(Shard &s) {
-  s.dp.sl_desc = s.d_sl_desc;
-  s.dp.sl_len = s.d_sl_len;
-  s.dp.sl_pos = s.d_sl_pos;
-  s.dp.sl_ppre = s.d_sl_ppre;
-  s.dp.sl_pos_bits = s.sl_pos_bits;
-  s.dp.sl_val = s.d_sl_val;
-  s.dp.n_slices = (int32_t)s.sl_desc_n;
+  s.dp.sl = s.built.sl;
   s.plan.row_slices = true;
   if (s.d_val) {
     s.dev.release(s.d_val);
@@ -858,23 +831,21 @@ static void use_slices(Shard &s) {
   }
 }
 
-static void use_slabs(Shard &s) {
-  s.dp.n_slabs = s.n_slabs;
-  s.dp.slab_rp = s.d_slab_rp;
-  s.dp.slab_col = s.d_slab_col;
-  s.dp.slab_val = s.d_slab_val;
-}
-
-// The launch's tables for one planned shard (needs s.plan and s.h_rp): the
-// serial bound, the split rows, which of the tables build_row_tables made
-// this launch shape can read (the others fall back to the 32-bit columns),
-// and the device copies of the x windows and the wave tasks.
+// The launch's tables for one planned shard (needs s.plan and s.host): the
+// serial bound, the split rows, which of the records build_row_tables left in
+// s.built this launch shape can read -- taken whole into s.dp; the others stay
+// empty there and the launch falls back to the 32-bit columns -- the device
+// copies of the x windows and the wave tasks, and the planned launch's terms
+// of s.saved.
 int build_plan_tables(Shard &s, unsigned flags) {
   const int kern = s.plan.kernel;
-  const bool tasks = kern == kCsr3 && !s.h_tasks.empty();
+  const bool tasks = kern == kCsr3 && !s.host.tasks.empty();
   const bool serial = s.tune.deterministic == HSPMV_DETERMINISTIC_SERIAL;  // every row by one lane, in order
   int rc;
   s.dp = DevPlan();
+  SavedTerms &t = s.saved;
+  t.dtype = s.dtype, t.val_dtype = s.val_dtype;
+  t.m = s.A.m, t.nnz = s.A.nnz, t.x_entries = s.x_entries;
   s.dp.serial_max = s.dtype == HSPMV_F32 ? kSerialMaxF32 : kSerialMax;  // by the vectors' dtype
   if (serial && kern != kStream && kern != kCsr3)
     return set_error(HSPMV_E_INVALID, "deterministic = 3 (serial order) needs the row kernels, and "
@@ -882,15 +853,16 @@ int build_plan_tables(Shard &s, unsigned flags) {
   if (serial) s.dp.serial_max = INT32_MAX;
   else if (s.tune.serial_max > 0) s.dp.serial_max = s.tune.serial_max;  // A/B knob (HSPMV_SERIAL_MAX, diagnostic builds)
   if (kern == kCsort) {  // long rows are slices of the csort blocks
-    s.dp.cs = s.csort;
-    s.plan.blocks = s.csort.n_wg;
-    s.plan.u = s.csort.u;
-    s.c16_saved = c16_saved_of(kFmtCsort, saved_terms(s, 0));
+    s.dp.cs = s.built.cs;
+    s.plan.blocks = t.blocks = s.dp.cs.n_wg;
+    s.plan.u = s.dp.cs.u;
+    s.c16_saved = c16_saved_of(kFmtCsort, t);
     return HSPMV_OK;
   }
   SplitPlan L;
-  if (kern != kVector && plan_split_rows(s.h_rp.data(), s.A.m, flags, L) && (rc = upload_split_rows(s, L)))
+  if (kern != kVector && plan_split_rows(s.host.rp.data(), s.A.m, flags, L) && (rc = upload_split_rows(s, L)))
     return rc;
+  s.dp.split = s.built.split;
   int format = kFmtCol32;
   if (kern == kVector) {  // the vector kernel reads 32-bit columns
     s.A.col16 = nullptr;
@@ -902,36 +874,38 @@ int build_plan_tables(Shard &s, unsigned flags) {
     const bool fits = (s.xd_shape == kStream && kern == kStream && s.plan.groups == 1 &&
                        s.plan.waves_per_block == 4) ||
                       (s.xd_shape == kCsr3 && tasks && s.plan.waves_per_block == s.A.task_waves);
-    if (fits) use_dict(s);
-    if (fits && s.d_sl_desc) use_slices(s);
+    const bool slices = s.built.sl.desc != nullptr;
+    if (fits) s.dp.xd = s.built.xd;
+    if (fits && slices) use_slices(s);
     if (!fits) {  // planned for another block shape: the kernels read the 32-bit columns
       s.A.col16 = nullptr;
       drop_slices(s);
     }
-    format = !fits ? kFmtCol32 : s.d_sl_desc ? kFmtSlices : kFmtDict;
+    format = !fits ? kFmtCol32 : slices ? kFmtSlices : kFmtDict;
   } else if (s.A.col16 && s.A.c16_mode == 2 && (kern != s.c16g_shape || (kern == kCsr3 && !tasks))) {
     s.A.col16 = nullptr;  // group bases built for another row grouping: 32-bit columns
     s.A.cbase = nullptr;
   } else if (s.A.col16) {
     format = s.A.c16_mode == 2 ? kFmtGroup16 : kFmtBlock16;
   }
-  if (s.n_slabs && (kern == kStream || kern == kCsr3)) {
-    use_slabs(s);
+  if (s.built.slabs.n && (kern == kStream || kern == kCsr3)) {
+    s.dp.slabs = s.built.slabs;
     format = kFmtSlabs;
   }
-  if (format != kFmtCol32) s.c16_saved = c16_saved_of(format, saved_terms(s, L.long_nnz));
-  const std::vector<int32_t> &xw = kern == kStream ? s.h_xwin : s.h_xwin_t;
+  t.long_nnz = L.long_nnz, t.blocks = s.plan.blocks, t.n_cplanes = s.A.n_cplanes;
+  t.groups = kern == kCsr3 ? (int64_t)s.host.tasks.size() - 1 : (s.A.m + 63) / 64;
+  if (format != kFmtCol32) s.c16_saved = c16_saved_of(format, t);
+  const std::vector<int32_t> &xw = kern == kStream ? s.host.xwin : s.host.xwin_t;
   if ((kern == kStream || tasks) && !xw.empty()) {
-    if ((rc = s.dev.upload(&s.d_xwin, xw.data(), 4 * xw.size()))) return rc;
-    s.dp.xwin = s.d_xwin;
+    if ((rc = s.dev.upload(&s.built.xwin, xw.data(), 4 * xw.size()))) return rc;
+    s.dp.xwin = s.built.xwin;
   }
-  std::vector<int32_t>().swap(s.h_xwin);
-  std::vector<int32_t>().swap(s.h_xwin_t);
   if (tasks) {
-    if ((rc = s.dev.upload(&s.d_task, s.h_tasks.data(), 4 * s.h_tasks.size()))) return rc;
-    s.dp.task_start = s.d_task;
-    s.dp.n_tasks = (int32_t)(s.h_tasks.size() - 1);
-    s.dp.task_align = ssr_aligned(s.tune) ? 1 : 0;
+    DevTasks &d = s.built.tasks;
+    if ((rc = s.dev.upload(&d.start, s.host.tasks.data(), 4 * s.host.tasks.size()))) return rc;
+    d.n = (int32_t)(s.host.tasks.size() - 1);
+    d.align = ssr_aligned(s.tune) ? 1 : 0;
+    s.dp.tasks = d;
   }
   return HSPMV_OK;
 }

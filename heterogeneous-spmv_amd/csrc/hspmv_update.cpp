@@ -14,13 +14,13 @@ namespace hspmv {
 //               16-bit columns, dictionaries, x windows), VECTOR, the split-row
 //               and the serial long-row kernels read.  A row-slice shard has
 //               released it, a borrowed one never had it (A.val is the caller's);
-//   row slices  d_sl_val, slice-major (build_slices);
-//   x slabs     d_slab_val, slab-major (plan_xslabs); split rows stay in A.val;
-//   column-sorted  the entry stream (csort.ent / csort.val), sorted by column
+//   row slices  dp.sl.val, slice-major (build_slices);
+//   x slabs     dp.slabs.val, slab-major (plan_xslabs); split rows stay in A.val;
+//   column-sorted  the entry stream (dp.cs.ent / dp.cs.val), sorted by column
 //               inside each workgroup and, under fixed-point slots, scaled per
 //               row by 2^rexp, which follows the values (build_csort).  Only a
 //               shard that kept the source index of every stream position
-//               (hspmv_create_updatable: csort.src) can restate it.
+//               (hspmv_create_updatable: dp.cs.src) can restate it.
 // An update puts the new CSR-order values where A.val points -- a copy into
 // d_val, or the caller's array itself for a borrowed shard -- and rebuilds, on
 // the shard's stream, each derived copy the DevPlan launches from
@@ -33,16 +33,16 @@ namespace hspmv {
 
 static int refresh_derived(Shard &s, const void *src) {
   hipStream_t st = s.dev.stream;
-  if (s.dp.sl_desc) {
-    const hipError_t e = launch_refresh_slices(s.val_dtype, s.dp.n_slices, s.dp.sl_desc, s.dp.sl_len,
-                                               s.A.row_ptr, src, s.d_sl_val, st);
+  if (s.dp.sl.desc) {
+    const hipError_t e = launch_refresh_slices(s.val_dtype, s.dp.sl.n, s.dp.sl.desc, s.dp.sl.len,
+                                               s.A.row_ptr, src, s.dp.sl.val, st);
     if (e != hipSuccess)
       return set_error(HSPMV_E_HIP, "row-slice value refresh on GPU %d failed: %s", s.dev.device,
                        hipGetErrorString(e));
   }
-  if (s.dp.n_slabs) {
-    const hipError_t e = launch_refresh_slabs(s.val_dtype, s.A.m, s.A.nnz, s.dp.n_slabs, s.A.row_ptr,
-                                              s.dp.slab_rp, src, s.d_slab_val, st);
+  if (s.dp.slabs.n) {
+    const hipError_t e = launch_refresh_slabs(s.val_dtype, s.A.m, s.A.nnz, s.dp.slabs.n, s.A.row_ptr,
+                                              s.dp.slabs.rp, src, s.dp.slabs.val, st);
     if (e != hipSuccess)
       return set_error(HSPMV_E_HIP, "x-slab value refresh on GPU %d failed: %s", s.dev.device,
                        hipGetErrorString(e));

@@ -245,7 +245,7 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   const int mode = s.tune.x_dict > 0 ? 1 : (s.tune.x_dict < 0 ? 0 : -1);  // -1 auto, 0 off, 1 on when it fits
   if (mode == 0 || (flags & HSPMV_FLAG_NO_COL16) || m == 0) return HSPMV_OK;
   if (mode < 0 && have_xwin) return HSPMV_OK;
-  const int kern = kernel_for_tables(s.A.n_ssr, !s.h_tasks.empty(), flags);
+  const int kern = kernel_for_tables(s.A.n_ssr, !s.host.tasks.empty(), flags);
   if (kern != kStream && kern != kCsr3) return HSPMV_OK;
   const int W = xd_block_tasks(s.tune, s.A.task_waves);
   if (kern == kCsr3 && W != 4 && W != 8) return HSPMV_OK;  // the XD kernels run 4 or 8 waves
@@ -256,7 +256,7 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
   const int32_t long_t = split_threshold(flags);
   XdPlan P;
   // (cuts the task table only when the dictionaries are taken)
-  std::vector<int32_t> tasks = s.h_tasks;
+  std::vector<int32_t> tasks = s.host.tasks;
   // row slices (hspmv_slices.cpp): decided from the rows and the options
   // before the dictionaries are planned, which are then sized for workgroups
   // without product staging
@@ -266,30 +266,31 @@ int build_xdict(Shard &s, const int32_t *rp, const int32_t *col, const void *val
                       s.tune, slices, true, P, &s.xd_cut))
     return HSPMV_OK;
   if (mode < 0 && 2 * P.entries > P.in_kernel_nnz) return HSPMV_OK;  // too little reuse to pay
-  s.h_tasks.swap(tasks);
+  s.host.tasks.swap(tasks);
   int rc;
   if (slices) {
     // the slice kernel reads the positions and values slice-major: only
     // those are uploaded (the CSR-order values go when the launch is
     // settled, build_plan_tables)
     SlicePlan S;
-    build_slices(rp, P.pos.data(), val, m, s.val_dtype, slice_starts(kern, m, s.h_tasks), S);
+    build_slices(rp, P.pos.data(), val, m, s.val_dtype, slice_starts(kern, m, s.host.tasks), S);
     if ((rc = upload_slices(s, S))) return rc;
     s.A.has_slices = true;
   } else if ((rc = s.dev.upload(&s.d_c16, P.pos.data(), 2 * P.pos.size()))) {
     return rc;
   }
-  if ((rc = s.dev.upload(&s.d_xd_blk, P.blk.data(), 4 * P.blk.size()))) return rc;
-  if ((rc = s.dev.upload(&s.d_xd_runs, P.rec.data(), 4 * P.rec.size()))) return rc;
-  s.A.col16 = slices ? s.d_sl_pos : s.d_c16;  // the 16-bit position stream the launch reads
+  DevXdict &d = s.built.xd;
+  if ((rc = s.dev.upload(&d.blk, P.blk.data(), 4 * P.blk.size()))) return rc;
+  if ((rc = s.dev.upload(&d.runs, P.rec.data(), 4 * P.rec.size()))) return rc;
+  s.A.col16 = slices ? s.built.sl.pos : s.d_c16;  // the 16-bit position stream the launch reads
   s.A.cbase = nullptr;
   s.A.cplanes = nullptr;
   s.A.n_cplanes = 0;
   s.xd_shape = kern;
   if (kern == kCsr3) s.A.task_waves = W;
-  s.xd_lds_bytes = (int32_t)((int64_t)P.tmax * (int64_t)sv);
-  s.xd_entries = P.entries;
-  s.xd_runs_n = (int64_t)P.rec.size() / 2;
+  d.lds_bytes = (int32_t)((int64_t)P.tmax * (int64_t)sv);
+  s.saved.xd_entries = P.entries;
+  s.saved.xd_runs_n = (int64_t)P.rec.size() / 2;
   return HSPMV_OK;
 }
 

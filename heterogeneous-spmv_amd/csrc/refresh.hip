@@ -28,7 +28,7 @@
 //
 //  * hspmv_refresh_slabs<TV, L>  the slab-major copy of the x slabs
 //      L lanes per row.  Segment b of row r is the next slab_rp_b[r + 1] -
-//      slab_rp_b[r] CSR entries of the row (build_xslabs, hspmv_tables.cpp),
+//      slab_rp_b[r] CSR entries of the row (plan_xslabs, hspmv_tables.cpp),
 //      so the lanes walk the B row-pointer arrays in slab order and copy each
 //      segment with consecutive lanes on consecutive entries.  Split rows have
 //      empty segments in every slab: nothing is copied for them (the split-row

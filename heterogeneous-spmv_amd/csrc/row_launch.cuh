@@ -28,18 +28,18 @@ inline uint32_t block_order(const LaunchPlan &p) {
 
 template <typename T, typename TV>
 hipError_t launch_slices(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st) {
-  if (!dp.xd_blk || !dp.sl_len || !dp.sl_pos || !dp.sl_val || p.waves_per_block != 4 ||
-      p.blocks != ((int64_t)dp.n_slices + 3) / 4 ||
-      !(dp.sl_pos_bits == 16 || (dp.sl_pos_bits == 12 && dp.sl_ppre)))
+  if (!dp.xd.blk || !dp.sl.len || !dp.sl.pos || !dp.sl.val || p.waves_per_block != 4 ||
+      p.blocks != ((int64_t)dp.sl.n + 3) / 4 ||
+      !(dp.sl.pos_bits == 16 || (dp.sl.pos_bits == 12 && dp.sl.ppre)))
     return hipErrorInvalidValue;  // the host built the slices for another block shape
-  const Slices sl{dp.sl_desc, dp.sl_len, dp.sl_pos, dp.sl_ppre};
-  const XDict xd{dp.xd_blk, reinterpret_cast<const int2 *>(dp.xd_runs)};
-  const unsigned dyn = (unsigned)dp.xd_lds_bytes + (unsigned)p.dyn_lds;
-  const TV *val = static_cast<const TV *>(dp.sl_val);
-  static_switch<12, 16>(dp.sl_pos_bits, [&](auto PB) {
+  const Slices sl{dp.sl.desc, dp.sl.len, dp.sl.pos, dp.sl.ppre};
+  const XDict xd{dp.xd.blk, reinterpret_cast<const int2 *>(dp.xd.runs)};
+  const unsigned dyn = (unsigned)dp.xd.lds_bytes + (unsigned)p.dyn_lds;
+  const TV *val = static_cast<const TV *>(dp.sl.val);
+  static_switch<12, 16>(dp.sl.pos_bits, [&](auto PB) {
     static_flag(p.nontemporal, [&](auto NT) {
       hipLaunchKernelGGL((hspmv_slices<T, NT, HSPMV_SLICE_BATCH, PB, TV>), dim3((unsigned)p.blocks), dim3(256), dyn,
-                         st, dp.n_slices, block_order(p), (int32_t)p.y_nt, sl, xd, val, x, y);
+                         st, dp.sl.n, block_order(p), (int32_t)p.y_nt, sl, xd, val, x, y);
     });
   });
   return hipGetLastError();
@@ -56,10 +56,10 @@ void launch_rows_shape(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, 
                        hipStream_t st) {
   const TV *val = static_cast<const TV *>(A.val);
   const ColSrc cs = col_src(A);
-  const XDict xd{dp.xd_blk, reinterpret_cast<const int2 *>(dp.xd_runs)};
+  const XDict xd{dp.xd.blk, reinterpret_cast<const int2 *>(dp.xd.runs)};
   const int2 *xw = reinterpret_cast<const int2 *>(dp.xwin);
   // dynamic LDS: the block's x dictionary (XD), or occupancy experiments (HSPMV_DYNLDS)
-  const unsigned dyn = XD ? (unsigned)dp.xd_lds_bytes + (unsigned)p.dyn_lds : (unsigned)p.dyn_lds;
+  const unsigned dyn = XD ? (unsigned)dp.xd.lds_bytes + (unsigned)p.dyn_lds : (unsigned)p.dyn_lds;
   const dim3 grid((unsigned)p.blocks);
   const int wpb = p.waves_per_block;
   if (p.kernel == kStream) {
@@ -73,7 +73,7 @@ void launch_rows_shape(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, 
         static_flag<!XD>(xw != nullptr, [&](auto XW) {
           static_flag<!XD && !PF>(p.lds_pad, [&](auto PAD) {
             hipLaunchKernelGGL((hspmv_csr_stream<T, NT, U, PF, C16, XW, XD, W, PAD, TV>), grid, dim3(W * 64), dyn,
-                               st, A.m, dp.long_t, dp.serial_max, block_order(p), (int32_t)p.groups,
+                               st, A.m, dp.split.long_t, dp.serial_max, block_order(p), (int32_t)p.groups,
                                (int32_t)p.y_nt, p.carry, A.row_ptr, cs, xw, xd, val, x, y);
           });
         });
@@ -87,9 +87,9 @@ void launch_rows_shape(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, 
     if constexpr (!XD || W >= 4) {
       // x windows: packed tasks only (4 per block), and none under a dictionary
       static_flag<!XD && W == 4>(xw != nullptr, [&](auto XW) {
-        hipLaunchKernelGGL((hspmv_csr3<T, NT, U, PF, C16, W, XW, XD, TV>), grid, dim3(W * 64), dyn, st, dp.n_tasks,
-                           dp.long_t, dp.serial_max, block_order(p), (int32_t)p.y_nt, p.carry, dp.task_align,
-                           dp.task_start, xw, xd, A.row_ptr, cs, val, x, y);
+        hipLaunchKernelGGL((hspmv_csr3<T, NT, U, PF, C16, W, XW, XD, TV>), grid, dim3(W * 64), dyn, st, dp.tasks.n,
+                           dp.split.long_t, dp.serial_max, block_order(p), (int32_t)p.y_nt, p.carry, dp.tasks.align,
+                           dp.tasks.start, xw, xd, A.row_ptr, cs, val, x, y);
       });
     }
   });
@@ -100,20 +100,20 @@ void launch_rows_shape(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, 
 // positions, so it has no col16 variants.
 enum { kCol32 = 0, kCol16Block = 1, kCol16Group = 2, kColDict = 3 };
 
-// TV: the stored type of A.val / dp.sl_val (the mixed handles: float under
+// TV: the stored type of A.val / dp.sl.val (the mixed handles: float under
 // T = double).
 template <typename T, typename TV = T>
 hipError_t launch_rows(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p, const T *x, T *y,
                        hipStream_t st) {
-  if (dp.sl_desc) return launch_slices<T, TV>(dp, p, x, y, st);  // row slices of a dictionary handle
+  if (dp.sl.desc) return launch_slices<T, TV>(dp, p, x, y, st);  // row slices of a dictionary handle
   int fmt = A.col16 ? kCol16Block : kCol32;
-  if (dp.xd_blk) {
+  if (dp.xd.blk) {
     if (!A.col16 || (p.kernel == kStream && p.groups != 1) ||
-        (p.kernel == kCsr3 && (!dp.task_start || (p.waves_per_block != 4 && p.waves_per_block != 8))))
+        (p.kernel == kCsr3 && (!dp.tasks.start || (p.waves_per_block != 4 && p.waves_per_block != 8))))
       return hipErrorInvalidValue;  // the host built the dictionary for another block shape
     fmt = kColDict;
   } else if (A.col16 && A.c16_mode == 2) {
-    if (p.kernel == kCsr3 && !dp.task_start)
+    if (p.kernel == kCsr3 && !dp.tasks.start)
       return hipErrorInvalidValue;  // built for the host-planned wave tasks (one base per task)
     fmt = kCol16Group;
   }

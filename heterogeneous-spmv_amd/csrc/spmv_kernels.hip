@@ -207,18 +207,19 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
   const int32_t *ci = A.col_idx;
   const TV *val = static_cast<const TV *>(A.val);
   hipError_t e = hipSuccess;
+  const DevSplit &sp = dp.split;
   // serial order: the long rows' workgroups start first, on their own
   // stream (forked from st, joined back below), beside the row kernel, and
-  // leave their sums in dp.partials for hspmv_long_scatter -- C5: 289 us of
+  // leave their sums in sp.partials for hspmv_long_scatter -- C5: 289 us of
   // x-slab passes and a 497 us add chain otherwise in sequence
-  const bool fork = dp.n_long > 0 && dp.long_serial && dp.long_stream;
+  const bool fork = sp.n_long > 0 && sp.long_serial && sp.long_stream;
   if (fork) {
-    if ((e = hipEventRecord(dp.long_fork, st)) != hipSuccess ||
-        (e = hipStreamWaitEvent(dp.long_stream, dp.long_fork, 0)) != hipSuccess)
+    if ((e = hipEventRecord(sp.long_fork, st)) != hipSuccess ||
+        (e = hipStreamWaitEvent(sp.long_stream, sp.long_fork, 0)) != hipSuccess)
       return e;
-    hipLaunchKernelGGL((hspmv_long_serial<T, NT, TV>), dim3((unsigned)dp.n_long), dim3(256), 0, dp.long_stream,
-                       dp.n_long, dp.long_row, rp, ci, val, x, y, static_cast<T *>(dp.partials));
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(dp.long_join, dp.long_stream)) != hipSuccess)
+    hipLaunchKernelGGL((hspmv_long_serial<T, NT, TV>), dim3((unsigned)sp.n_long), dim3(256), 0, sp.long_stream,
+                       sp.n_long, sp.long_row, rp, ci, val, x, y, static_cast<T *>(sp.partials));
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(sp.long_join, sp.long_stream)) != hipSuccess)
       return e;
   }
   switch (p.kernel) {
@@ -231,17 +232,17 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
       return hipGetLastError();  // the vector kernel sums split rows itself
     case kStream:
     case kCsr3:
-      if (dp.n_slabs > 0) {  // one pass per x slab, each continuing the rows from y
+      if (dp.slabs.n > 0) {  // one pass per x slab, each continuing the rows from y
         DevCSR As = A;
-        As.col_idx = dp.slab_col;
-        As.val = dp.slab_val;
+        As.col_idx = dp.slabs.col;
+        As.val = dp.slabs.val;
         As.col16 = nullptr;
         As.cbase = nullptr;
         As.cplanes = nullptr;
         As.n_cplanes = 0;
         LaunchPlan ps = p;
-        for (int32_t b = 0; b < dp.n_slabs && e == hipSuccess; ++b) {
-          As.row_ptr = dp.slab_rp + (size_t)b * (size_t)(A.m + 1);
+        for (int32_t b = 0; b < dp.slabs.n && e == hipSuccess; ++b) {
+          As.row_ptr = dp.slabs.rp + (size_t)b * (size_t)(A.m + 1);
           ps.carry = b > 0;
           e = launch_rows_of<TV>(As, dp, ps, x, y, st);  // (mixed: slab_val is fp32 as well)
         }
@@ -258,20 +259,19 @@ hipError_t launch_typed(const DevCSR &A, const DevPlan &dp, const LaunchPlan &p,
   }
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (fork) {
-    if ((e = hipStreamWaitEvent(st, dp.long_join, 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL((hspmv_long_scatter<T>), dim3((unsigned)((dp.n_long + 255) / 256)), dim3(256), 0, st,
-                       dp.n_long, dp.long_row, static_cast<const T *>(dp.partials), y);
+    if ((e = hipStreamWaitEvent(st, sp.long_join, 0)) != hipSuccess) return e;
+    hipLaunchKernelGGL((hspmv_long_scatter<T>), dim3((unsigned)((sp.n_long + 255) / 256)), dim3(256), 0, st,
+                       sp.n_long, sp.long_row, static_cast<const T *>(sp.partials), y);
     e = hipGetLastError();
-  } else if (dp.n_long > 0 && dp.long_serial) {
-    hipLaunchKernelGGL((hspmv_long_serial<T, NT, TV>), dim3((unsigned)dp.n_long), dim3(256), 0, st, dp.n_long,
-                       dp.long_row, rp, ci, val, x, y, static_cast<T *>(nullptr));
+  } else if (sp.n_long > 0 && sp.long_serial) {
+    hipLaunchKernelGGL((hspmv_long_serial<T, NT, TV>), dim3((unsigned)sp.n_long), dim3(256), 0, st, sp.n_long,
+                       sp.long_row, rp, ci, val, x, y, static_cast<T *>(nullptr));
     e = hipGetLastError();
-  } else if (dp.n_long > 0) {
-    hipLaunchKernelGGL((hspmv_long_chunks<T, NT, TV>), dim3((unsigned)dp.n_chunks), dim3(256), 0, st,
-                       dp.n_chunks, dp.chunk_k, ci, val, x, static_cast<T *>(dp.partials));
-    hipLaunchKernelGGL((hspmv_long_reduce<T>), dim3((unsigned)((dp.n_long + 3) / 4)), dim3(256),
-                       0, st, dp.n_long, dp.long_row, dp.long_cstart,
-                       static_cast<const T *>(dp.partials), y);
+  } else if (sp.n_long > 0) {
+    hipLaunchKernelGGL((hspmv_long_chunks<T, NT, TV>), dim3((unsigned)sp.n_chunks), dim3(256), 0, st,
+                       sp.n_chunks, sp.chunk_k, ci, val, x, static_cast<T *>(sp.partials));
+    hipLaunchKernelGGL((hspmv_long_reduce<T>), dim3((unsigned)((sp.n_long + 3) / 4)), dim3(256), 0, st, sp.n_long,
+                       sp.long_row, sp.long_cstart, static_cast<const T *>(sp.partials), y);
     e = hipGetLastError();
   }
   return e;

@@ -48,8 +48,10 @@ def fields(st):
 
 
 def spmv_case(L, A, maps=None, kernel="auto", flags=0, options=None, devices=None, vector_dtype=None,
-              borrowed=False):
-    """(info, y) of one handle of library L."""
+              borrowed=False, updatable=False, update=False):
+    """(info, y) of one handle of library L.  updatable: created by
+    hspmv_create_updatable; update: one hspmv_update_values (host memory, other
+    values) before the SpMV, so y and the report are those after the refresh."""
     vdt = np.dtype(A.val.dtype if vector_dtype is None else vector_dtype)
     keep = []
     if borrowed:  # the matrix arrays stay the caller's (HSPMV_FLAG_DEVICE_PTRS)
@@ -62,12 +64,18 @@ def spmv_case(L, A, maps=None, kernel="auto", flags=0, options=None, devices=Non
     ms = maps.c_struct() if maps is not None else None
     opt = _lib.make_options(_KERNELS[kernel] | flags, options, devices=devices)
     h = C.c_void_p()
-    if vdt != A.val.dtype:
+    if updatable:
+        rc = L.hspmv_create_updatable(C.byref(h), C.byref(cs), C.byref(ms) if ms else None, C.byref(opt),
+                                      dtype_code(vdt))
+    elif vdt != A.val.dtype:
         rc = L.hspmv_create_mixed(C.byref(h), C.byref(cs), C.byref(ms) if ms else None, C.byref(opt),
                                   dtype_code(vdt))
     else:
         rc = L.hspmv_create_ex(C.byref(h), C.byref(cs), C.byref(ms) if ms else None, C.byref(opt))
     assert rc == 0, L.hspmv_last_error()
+    if update:
+        v2 = np.ascontiguousarray(A.val * A.val.dtype.type(0.75) - A.val.dtype.type(0.5))
+        assert L.hspmv_update_values(h, v2.ctypes.data, 0) == 0, L.hspmv_last_error()
     inf = _lib.Info()
     assert L.hspmv_get_info_sized(h, C.byref(inf), C.sizeof(inf)) == 0
     x = gen.rand_x(A.n, 42).astype(vdt)
@@ -143,6 +151,10 @@ def families():
         yield f"csort_{tag}", lambda L, A=A, o=o: S(L, A, kernel="csort", options=o)
         yield (f"csort_{tag}_reproducible",
                lambda L, A=A, o=o: S(L, A, kernel="csort", options={**o, "deterministic": 2}))
+    # new values before the SpMV (hspmv_update_values): the refresh of the
+    # column-sorted entry stream of an updatable handle, and of the row slices
+    yield "csort_updatable_update", lambda L: S(L, pl, kernel="csort", updatable=True, update=True)
+    yield "slices_pos12_update", lambda L: S(L, st21, kernel="stream", options=ON, update=True)
     yield "long_rows", lambda L: S(L, lr)
     yield "long_rows_serial", lambda L: S(L, lr, options={"deterministic": 3})
     yield "devices_0_0", lambda L: S(L, lap, devices=[0, 0])

@@ -503,7 +503,7 @@ def group_spans(A, skip_split=False):
 
 def col16_planes(A):
     """High-bit planes of the block-base col16 format (hspmv_tables.cpp
-    build_col16): bits of the widest 256-nonzero block's span, less 16."""
+    plan_col16): bits of the widest 256-nonzero block's span, less 16."""
     col = A.col_idx.astype(np.int64)
     span = max(int(col[k:k + C16_BLOCK].max() - col[k:k + C16_BLOCK].min())
                for k in range(0, A.nnz, C16_BLOCK))
