@@ -55,6 +55,16 @@
 //                       sum over the last round's values (not with --rhs;
 //                       a band-k order keeps its permutation: the values are
 //                       those of the matrix the handle was created from)
+//   --axpby ALPHA,BETA  after the timed loop, its report and the check: y0 =
+//                       the --x generator with seed SEED + 1 (m entries); one
+//                       hspmv_spmv_axpby(ALPHA, BETA) over it is compared byte
+//                       for byte with the host model formed from the device's
+//                       own s = A x ("AxpbyCheck: PASS|FAIL rows_differ=N
+//                       path=fused|two_pass"); then hspmv_run_axpby is timed
+//                       from y0 and printed as "AxpbyTimeMin:" / "AxpbyTimeMax:"
+//                       / "AxpbyTimeAvg:" (wall) and "AxpbyKernelMin:" (not
+//                       with --rhs or --gpus > 1; keep |BETA| < 1: y evolves
+//                       over the timed calls)
 //   --dump-y PATH       write y as raw binary (dtype) for external checks
 //   --no-check          skip the serial CPU check
 #pragma once
@@ -86,6 +96,8 @@ struct Options {
   bool check = true;
   int rhs = 0;  // > 0: the multi-vector operator with this many right-hand sides
   int update_values = 0;  // > 0: rounds of hspmv_update_values after the timed loop
+  bool axpby = false;     // --axpby ALPHA,BETA: hspmv_spmv_axpby checked, hspmv_run_axpby timed
+  double alpha = 1.0, beta = 0.0;
   std::string dump_y;
   std::string params = "mi355x";
   bool bandk = true;  // spmv-csrk on a .csr: band-k reorder (the reference's CSRk_Graph)
@@ -162,6 +174,15 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
       const char *v = need("--update-values"); if (!v) return false;
       o.update_values = atoi(v);
       if (o.update_values < 1) { fprintf(stderr, "bad --update-values %s (>= 1)\n", v); return false; }
+    } else if (a == "--axpby") {
+      const char *v = need("--axpby"); if (!v) return false;
+      char *end = nullptr;
+      o.alpha = strtod(v, &end);
+      if (end == v || *end != ',') { fprintf(stderr, "bad --axpby %s (ALPHA,BETA)\n", v); return false; }
+      const char *b = end + 1;
+      o.beta = strtod(b, &end);
+      if (end == b || *end != '\0') { fprintf(stderr, "bad --axpby %s (ALPHA,BETA)\n", v); return false; }
+      o.axpby = true;
     } else if (a == "--no-check") {
       o.check = false;
     } else if (a == "--dump-y") {
@@ -185,6 +206,11 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
       return false;
     }
     if (o.update_values > 0) { fprintf(stderr, "--rhs takes no --update-values\n"); return false; }
+    if (o.axpby) { fprintf(stderr, "--rhs takes no --axpby\n"); return false; }
+  }
+  if (o.axpby && o.gpus != 1) {
+    fprintf(stderr, "--axpby runs on one GPU (not --gpus %d)\n", o.gpus);
+    return false;
   }
   return true;
 }
@@ -330,6 +356,49 @@ inline int run_and_report_mm(const hspmv_csr_buf &A, int num_runs, const Options
   return rc;
 }
 
+// --axpby: s holds the device's y = A x (m entries of T, the handle's vector
+// type).  One hspmv_spmv_axpby over y0 against the host model -- the two
+// products and the sum each rounded to T on their own (the volatiles keep the
+// host compiler from contracting them) -- byte for byte, then hspmv_run_axpby
+// from y0.  Returns 0, 2 for a failed check, 1 after a library error.
+template <typename T>
+int run_axpby(hspmv_handle *h, int64_t m, const void *s_bytes, int num_runs, const Options &o,
+              const int32_t *perm) {
+  const T *s = (const T *)s_bytes;
+  Options oy = o;
+  oy.seed = o.seed + 1;
+  std::vector<double> y64;
+  fill_x(oy, m, y64);
+  std::vector<T> y0((size_t)(m ? m : 1)), got(y0.size());
+  for (int64_t i = 0; i < m; ++i) y0[(size_t)i] = (T)y64[(size_t)(perm ? perm[i] : i)];
+  const int path = hspmv_axpby_path(h);
+  if (path < 0) return die("hspmv_axpby_path");
+  if (hspmv_set_y(h, y0.data()) != HSPMV_OK) return die("hspmv_set_y");
+  if (hspmv_spmv_axpby(h, o.alpha, o.beta) != HSPMV_OK) return die("hspmv_spmv_axpby");
+  if (hspmv_get_y(h, got.data()) != HSPMV_OK) return die("hspmv_get_y");
+  const T alpha = (T)o.alpha, beta = (T)o.beta;
+  long long differ = 0;
+  for (int64_t i = 0; i < m; ++i) {
+    volatile T want = alpha * s[i];
+    if (beta != T(0)) {
+      volatile T by = beta * y0[(size_t)i];
+      want = want + by;
+    }
+    const T w = want;
+    if (memcmp(&w, &got[(size_t)i], sizeof(T)) != 0) differ++;
+  }
+  printf("AxpbyCheck: %s rows_differ=%lld path=%s\n", differ ? "FAIL" : "PASS", differ,
+         path == HSPMV_AXPBY_PATH_FUSED ? "fused" : "two_pass");
+  if (hspmv_set_y(h, y0.data()) != HSPMV_OK) return die("hspmv_set_y");
+  hspmv_timing t;
+  if (hspmv_run_axpby(h, o.alpha, o.beta, 5, num_runs, &t) != HSPMV_OK) return die("hspmv_run_axpby");
+  printf("AxpbyTimeMin: %lg\n", t.wall_min);
+  printf("AxpbyTimeMax: %lg\n", t.wall_max);
+  printf("AxpbyTimeAvg: %lg\n", t.wall_avg);
+  printf("AxpbyKernelMin: %lg\n", t.t_min);
+  return differ ? 2 : 0;
+}
+
 // Runs the timed protocol on an already-read matrix and prints the report.
 // perm (optional, m entries): A is the band-k permutation of the file's
 // matrix, row i = file row perm[i]; x is generated in file order and
@@ -446,6 +515,12 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
       printf("Bitwise: %lld rows differ\n", (long long)r.bit_diff);
       if (r.bit_diff) rc = 2;
     }
+  }
+  if (o.axpby) {
+    const int arc = vdt == HSPMV_F64 ? run_axpby<double>(h, A.m, y.data(), num_runs, o, perm)
+                                     : run_axpby<float>(h, A.m, y.data(), num_runs, o, perm);
+    if (arc == 1) return 1;
+    if (arc) rc = arc;
   }
   if (o.update_values > 0) {
     // new values on the planned handle, N rounds: round k holds the file's

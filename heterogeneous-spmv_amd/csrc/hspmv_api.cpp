@@ -104,11 +104,69 @@ bool shard_reverse(const hspmv_handle *h, const Shard &s) {
   return h->sweep_phase && shard_alternates(h, s);
 }
 
-// One SpMV of shard s on its stream (its device is the current one).
-int launch_shard(const hspmv_handle *h, Shard &s) {
-  hipError_t e = launch_spmv(s.A, s.dp, h->dtype, h->val_dtype, s.plan, s.x, s.y, s.dev.stream, shard_reverse(h, s));
+// One SpMV of shard s on its stream (its device is the current one), into
+// y (nullptr: the shard's y in use).
+int launch_shard(const hspmv_handle *h, Shard &s, void *y = nullptr) {
+  hipError_t e = launch_spmv(s.A, s.dp, h->dtype, h->val_dtype, s.plan, s.x, y ? y : s.y, s.dev.stream,
+                             shard_reverse(h, s));
   if (e != hipSuccess)
     return set_error(HSPMV_E_HIP, "SpMV launch on GPU %d failed: %s", s.dev.device, hipGetErrorString(e));
+  return HSPMV_OK;
+}
+
+// ---- y = alpha A x + beta y (hspmv_spmv_axpby)
+
+// The refusal every axpby entry point and hspmv_set_y share: a handle, and one
+// shard.  No device call.
+int check_single_shard(hspmv_handle *h, const char *what) {
+  int rc;
+  if ((rc = check_handle(h))) return rc;
+  if (h->shards.size() > 1)
+    return set_error(HSPMV_E_INVALID, "%s needs a single-device handle (this one has %d shards)", what,
+                     (int)h->shards.size());
+  return HSPMV_OK;
+}
+
+// Whether the next hspmv_spmv_axpby runs hspmv_slices_axpby (else SpMV into
+// the scratch vector, then hspmv_axpby).
+bool axpby_fused(const hspmv_handle *h) {
+  const Shard &s = h->shards[0];
+  return h->axpby_mode == HSPMV_AXPBY_AUTO && (s.plan.kernel == kStream || s.plan.kernel == kCsr3) &&
+         axpby_fusable(s.A, s.dp);
+}
+
+// Everything an axpby call decides before its first launch: the refusals,
+// and the two-pass path's scratch vector (allocated once, then kept).  The
+// shard's device is the current one on return.
+int prepare_axpby(hspmv_handle *h, const char *what) {
+  int rc;
+  if ((rc = check_single_shard(h, what))) return rc;
+  if (!h->x_set) return set_error(HSPMV_E_STATE, "x not set (hspmv_set_x / hspmv_bind_x_device)");
+  Shard &s = h->shards[0];
+  if (s.x == s.y && h->m > 0)
+    return set_error(HSPMV_E_INVALID, "%s: x and y are the same device array (y is read and written row by row "
+                                      "while other rows still gather from x)", what);
+  HIP_TRY(hipSetDevice(s.dev.device));
+  if (!axpby_fused(h) && !s.d_axpby && (rc = s.dev.alloc(&s.d_axpby, dtype_size(h->dtype) * (size_t)h->m)))
+    return rc;
+  return HSPMV_OK;
+}
+
+// One y = alpha A x + beta y on the shard's stream (prepare_axpby has passed);
+// flips the sweep phase as one hspmv_spmv does.
+int enqueue_axpby(hspmv_handle *h, const AxpbyScalars &ab) {
+  Shard &s = h->shards[0];
+  hipError_t e;
+  if (axpby_fused(h)) {
+    e = launch_spmv_axpby(s.A, s.dp, h->dtype, h->val_dtype, s.plan, ab, s.x, s.y, s.dev.stream,
+                          shard_reverse(h, s));
+  } else {
+    if (int rc = launch_shard(h, s, s.d_axpby)) return rc;
+    e = launch_axpby(h->dtype, h->m, ab, s.plan.y_nt, s.d_axpby, s.y, s.dev.stream);
+  }
+  if (e != hipSuccess)
+    return set_error(HSPMV_E_HIP, "axpby launch on GPU %d failed: %s", s.dev.device, hipGetErrorString(e));
+  h->sweep_phase = !h->sweep_phase;
   return HSPMV_OK;
 }
 
@@ -375,6 +433,63 @@ int hspmv_spmv(hspmv_handle *h) {
     if ((rc = launch_shard(h, s))) return rc;
   }
   h->sweep_phase = !h->sweep_phase;
+  return HSPMV_OK;
+}
+
+int hspmv_spmv_axpby(hspmv_handle *h, double alpha, double beta) {
+  int rc;
+  if ((rc = prepare_axpby(h, "hspmv_spmv_axpby"))) return rc;
+  return enqueue_axpby(h, AxpbyScalars{alpha, beta});
+}
+
+int hspmv_run_axpby(hspmv_handle *h, double alpha, double beta, int warmup, int iters, hspmv_timing *out) {
+  clear_error();
+  int rc;
+  if ((rc = check_single_shard(h, "hspmv_run_axpby"))) return rc;
+  if (!out || iters < 1 || warmup < 0) return set_error(HSPMV_E_INVALID, "bad arguments");
+  if ((rc = prepare_axpby(h, "hspmv_run_axpby"))) return rc;
+  const AxpbyScalars ab{alpha, beta};
+  std::vector<DevCtx *> devs{&h->shards[0].dev};
+  if ((rc = timed_run(devs, warmup, iters, [&](size_t) { return enqueue_axpby(h, ab); }, out))) return rc;
+  const double tmin = out->t_min;
+  // the SpMV's algorithmic bytes plus the one pass the general form adds: y_old
+  const double bytes = alg_bytes_of(h->m, h->x_entries(), h->nnz, h->dtype, h->val_dtype, h->n_ssr, h->n_sr) +
+                       ((beta != 0.0) ? (double)dtype_size(h->dtype) * (double)h->m : 0.0);
+  out->gflops = tmin > 0 ? 2.0 * (double)h->nnz / tmin * 1e-9 : 0.0;
+  out->gbps_alg = tmin > 0 ? bytes / tmin * 1e-9 : 0.0;
+  out->num_gpus = 1;
+  return HSPMV_OK;
+}
+
+int hspmv_set_axpby_path(hspmv_handle *h, int mode) {
+  clear_error();
+  int rc;
+  if ((rc = check_handle(h))) return rc;
+  if (mode != HSPMV_AXPBY_AUTO && mode != HSPMV_AXPBY_TWO_PASS)
+    return set_error(HSPMV_E_INVALID, "axpby path %d (HSPMV_AXPBY_AUTO or _TWO_PASS)", mode);
+  h->axpby_mode = mode;
+  return HSPMV_OK;
+}
+
+int hspmv_axpby_path(hspmv_handle *h) {
+  clear_error();
+  int rc;
+  if ((rc = check_single_shard(h, "hspmv_axpby_path"))) return rc;
+  return axpby_fused(h) ? HSPMV_AXPBY_PATH_FUSED : HSPMV_AXPBY_PATH_TWO_PASS;
+}
+
+int hspmv_set_y(hspmv_handle *h, const void *y_host) {
+  clear_error();
+  int rc;
+  if ((rc = check_single_shard(h, "hspmv_set_y"))) return rc;
+  if (!y_host && h->m > 0) return set_error(HSPMV_E_INVALID, "y is NULL");
+  Shard &s = h->shards[0];
+  const size_t bytes = dtype_size(h->dtype) * (size_t)h->m;
+  HIP_TRY(hipSetDevice(s.dev.device));
+  if (bytes) {
+    HIP_TRY(hipMemcpyAsync(s.y, y_host, bytes, hipMemcpyHostToDevice, s.dev.stream));
+    HIP_TRY(hipStreamSynchronize(s.dev.stream));
+  }
   return HSPMV_OK;
 }
 

@@ -400,6 +400,36 @@ hipError_t launch_csort(const DevCsort &c, int dtype, const void *x, void *y, hi
 hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, int val_dtype, const LaunchPlan &plan,
                        const void *x, void *y, hipStream_t stream, bool reverse = false);
 
+// ---- y = alpha (A x) + beta y (hspmv_spmv_axpby).  The
+// scalars as the caller gave them; each launch converts them to the vectors'
+// type once, on the host.
+struct AxpbyScalars {
+  double alpha, beta;
+};
+// Whether the fused path can run the shard: its launch is the slice kernel
+// alone (no x slabs, no split rows beside it).
+inline bool axpby_fusable(const DevCSR &A, const DevPlan &dp) {
+  return A.m > 0 && dp.sl.desc && dp.slabs.n == 0 && dp.split.n_long == 0;
+}
+// The fused path: hspmv_slices_axpby in place of hspmv_slices (the stream_*
+// units hold the instantiations); y is read (beta != 0) and written.
+hipError_t launch_slices_axpby_f32(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                   const float *x, float *y, hipStream_t st);
+hipError_t launch_slices_axpby_f64(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                   const double *x, double *y, hipStream_t st);
+hipError_t launch_slices_axpby_f32v64(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                      const double *x, double *y, hipStream_t st);
+// launch_spmv's counterpart for a shard that is axpby_fusable (else
+// hipErrorInvalidValue): one kernel, the sweep direction as there.
+hipError_t launch_spmv_axpby(const DevCSR &A, const DevPlan &dp, int dtype, int val_dtype, const LaunchPlan &plan,
+                             const AxpbyScalars &ab, const void *x, void *y, hipStream_t stream,
+                             bool reverse = false);
+// The two-pass path's second pass (axpby.hip): y[i] = alpha s[i] + beta y[i]
+// for m elements of dtype, y never read when beta converts to 0; y_nt: the
+// plan's nontemporal y stores.  s and y must not overlap.
+hipError_t launch_axpby(int dtype, int64_t m, const AxpbyScalars &ab, bool y_nt, const void *s, void *y,
+                        hipStream_t stream);
+
 // ---- value refresh (refresh.hip; hspmv_update_values, hspmv_update.cpp):
 // the derived copies of the values rebuilt on the device from src, the new
 // values in the shard's CSR order (val_dtype: the stored values').  Both

@@ -180,6 +180,7 @@ struct Shard {
   void *d_x = nullptr;     // own x (n entries)
   void *d_y = nullptr;     // own y (m_shard entries) -- or a view into d_yfull
   void *d_yfull = nullptr; // multi-GPU: padded all-gather buffer P*max_rows
+  void *d_axpby = nullptr; // hspmv_spmv_axpby's two-pass scratch (m entries; from the first such call on)
   const void *x = nullptr; // x in use (own or bound)
   void *y = nullptr;       // y in use (own or bound)
   int64_t x_entries = 0;   // distinct columns of this shard
@@ -214,6 +215,7 @@ struct hspmv_handle {
   // flip per hspmv_spmv / hspmv_run iteration, the same for every shard)
   int sweep_mode = HSPMV_SWEEP_AUTO;
   bool sweep_phase = false;
+  int axpby_mode = HSPMV_AXPBY_AUTO;  // hspmv_set_axpby_path
 };
 
 namespace hspmv {

@@ -4,7 +4,8 @@
 // (one per dtype, so hipcc compiles them in parallel); host code only.
 //
 // The variants of one unit, per NT in {0, 1} and U in {2, 3, 4, 5, 6, 8, 16}
-// (90 kernels, 36 of them with prefetch), plus the 4 slice kernels:
+// (90 kernels, 36 of them with prefetch), plus the 4 slice kernels (and their
+// 4 hspmv_slices_axpby twins, launch_slices):
 //   column format   STREAM                               CSR3
 //   32-bit, col16   W in {1, 2, 4} x windows on / off    W in {1, 2, 4, 8}, and
 //   modes 1 and 2   x padded on / off (no padding with   W = 4 with x windows
@@ -26,8 +27,11 @@ inline uint32_t block_order(const LaunchPlan &p) {
   return (uint32_t)p.xcd_chunk | (p.reverse ? kSweepReverse : 0u);
 }
 
+// ab: nullptr runs hspmv_slices (y = A x); else hspmv_slices_axpby with the
+// two scalars converted to T here, once (y = alpha (A x) + beta y).
 template <typename T, typename TV>
-hipError_t launch_slices(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st) {
+hipError_t launch_slices(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st,
+                         const AxpbyScalars *ab = nullptr) {
   if (!dp.xd.blk || !dp.sl.len || !dp.sl.pos || !dp.sl.val || p.waves_per_block != 4 ||
       p.blocks != ((int64_t)dp.sl.n + 3) / 4 ||
       !(dp.sl.pos_bits == 16 || (dp.sl.pos_bits == 12 && dp.sl.ppre)))
@@ -38,8 +42,13 @@ hipError_t launch_slices(const DevPlan &dp, const LaunchPlan &p, const T *x, T *
   const TV *val = static_cast<const TV *>(dp.sl.val);
   static_switch<12, 16>(dp.sl.pos_bits, [&](auto PB) {
     static_flag(p.nontemporal, [&](auto NT) {
-      hipLaunchKernelGGL((hspmv_slices<T, NT, HSPMV_SLICE_BATCH, PB, TV>), dim3((unsigned)p.blocks), dim3(256), dyn,
-                         st, dp.sl.n, block_order(p), (int32_t)p.y_nt, sl, xd, val, x, y);
+      if (ab)
+        hipLaunchKernelGGL((hspmv_slices_axpby<T, NT, HSPMV_SLICE_BATCH, PB, TV>), dim3((unsigned)p.blocks),
+                           dim3(256), dyn, st, dp.sl.n, block_order(p), (int32_t)p.y_nt, (T)ab->alpha, (T)ab->beta,
+                           sl, xd, val, x, y);
+      else
+        hipLaunchKernelGGL((hspmv_slices<T, NT, HSPMV_SLICE_BATCH, PB, TV>), dim3((unsigned)p.blocks), dim3(256),
+                           dyn, st, dp.sl.n, block_order(p), (int32_t)p.y_nt, sl, xd, val, x, y);
     });
   });
   return hipGetLastError();

@@ -1,6 +1,7 @@
 // slice_kernel.cuh -- hspmv_slices, the lane-per-row kernel of dictionary
 // handles with row slices (STREAM / CSR3 handles; instantiated beside the row
-// kernels, row_launch.cuh).  Device code only.
+// kernels, row_launch.cuh), and hspmv_slices_axpby, its twin whose store is
+// the y = alpha (A x) + beta y epilogue.  Device code only.
 //
 // The transposed (sliced-ELL) shape of the dictionary kernels, for handles
 // whose every row is summed serially anyway (hspmv_slices.cpp holds the
@@ -172,16 +173,59 @@ __device__ __forceinline__ T slice_consume(T acc, const SliceBatch<TV, B> &q, co
   return acc;
 }
 
+// What a slice kernel does with a row's sum before it is stored.  `before`
+// runs ahead of the slot loop, for the lanes that own a row, and what it
+// returns is handed to `after` with the sum.
+// hspmv_slices: the sum as it is.
+template <typename T>
+struct SliceStoreSum {
+  struct Old {};
+  __device__ __forceinline__ Old before(const T *, int32_t) const { return Old{}; }
+  __device__ __forceinline__ T after(T acc, Old) const { return acc; }
+};
+
+// Where SliceAxpby issues its load of the old y: 1 before the slot loop (the
+// load's latency under the whole slice, its registers held through it), 0
+// after it.
+#ifndef HSPMV_SLICE_YLOAD_EARLY
+#define HSPMV_SLICE_YLOAD_EARLY 1
+#endif
+
+// hspmv_slices_axpby: fl(fl(alpha s) + fl(beta y_old)), every operation
+// rounded on its own (-ffp-contract=off), or fl(alpha s) alone when beta == 0
+// -- a kernel-uniform branch that issues no load of y.
+template <typename T>
+struct SliceAxpby {
+  T alpha, beta;
+  struct Old {
+    const T *p;
+    T v;
+  };
+  __device__ __forceinline__ Old before(const T *y, int32_t row) const {
+    Old o{y + row, T(0)};
+    if (HSPMV_SLICE_YLOAD_EARLY && beta != T(0)) o.v = *o.p;
+    return o;
+  }
+  __device__ __forceinline__ T after(T acc, Old o) const {
+    const T as = alpha * acc;
+    if (beta == T(0)) return as;
+    if (!HSPMV_SLICE_YLOAD_EARLY) o.v = *o.p;
+    const T by = beta * o.v;
+    return as + by;
+  }
+};
+
 // One workgroup = one dictionary block (four wave tasks, or a half block's
 // two and two empty ones), staged by stage_xdict exactly as in the chunked
 // kernels.  Each wave reads its slice's descriptor (one scalar load) and its
 // rows' lengths before the staging; after the barrier it walks the slot
 // columns in batches of B, the next batch's loads issued before the current
 // one is consumed.  LDS: the dictionary alone.  Same bits as the row kernels.
-template <typename T, bool NT, int B, int PB, typename TV = T>
-__global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t blk_order, int32_t y_nt,
-                                                    Slices sl, XDict xd, const TV *__restrict__ val,
-                                                    const T *__restrict__ x, T *__restrict__ y) {
+// The body of both kernels below: EP is SliceStoreSum or SliceAxpby.
+template <typename T, bool NT, int B, int PB, typename TV, typename EP>
+__device__ __forceinline__ void slices_body(int32_t n_slices, uint32_t blk_order, int32_t y_nt, const Slices &sl,
+                                            const XDict &xd, const TV *__restrict__ val,
+                                            const T *__restrict__ x, T *y, const EP &ep) {
   static_assert(B % 4 == 0 && B >= 4, "batches hold whole position groups");
   static_assert(PB == 16 || (PB == 12 && B % 8 == 0), "12-bit positions come in groups of 8 slots");
   static_assert(B % (16 / (int)sizeof(TV)) == 0, "batches hold whole 16-byte value groups");
@@ -203,6 +247,8 @@ __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t b
   if (lane < nr) len = (int32_t)sl.len[r0 + lane];
   stage_xdict<T, 256>(reinterpret_cast<T *>(xdyn), x, xd, blk, threadIdx.x);
   if (nr <= 0) return;
+  typename EP::Old old{};
+  if (lane < nr) old = ep.before(y, r0 + lane);  // (the last slice's idle lanes address past row m)
   const T *xs = reinterpret_cast<const T *>(xdyn);
   const gchar *vb = uniform_ptr(val + (int64_t)off * kWave);
   const gchar *pb = uniform_ptr(sl.pos + (int64_t)poff * kWave);
@@ -239,11 +285,33 @@ __global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t b
   if constexpr (diag(kDiagNoStore)) {  // ablation: no y stores (kept live)
     if (lane < nr && acc == T(12345.678)) y[r0 + lane] = acc;
   } else if (lane < nr) {
+    const T out = ep.after(acc, old);
     if (y_nt)
-      __builtin_nontemporal_store(acc, y + r0 + lane);
+      __builtin_nontemporal_store(out, y + r0 + lane);
     else
-      y[r0 + lane] = acc;
+      y[r0 + lane] = out;
   }
+}
+
+// y = A x.
+template <typename T, bool NT, int B, int PB, typename TV = T>
+__global__ __launch_bounds__(256) void hspmv_slices(int32_t n_slices, uint32_t blk_order, int32_t y_nt,
+                                                    Slices sl, XDict xd, const TV *__restrict__ val,
+                                                    const T *__restrict__ x, T *__restrict__ y) {
+  slices_body<T, NT, B, PB, TV>(n_slices, blk_order, y_nt, sl, xd, val, x, y, SliceStoreSum<T>{});
+}
+
+// y = alpha (A x) + beta y (hspmv_spmv_axpby's fused path): hspmv_slices with
+// the epilogue between the row's sum -- the bits hspmv_slices stores -- and
+// its store.  The load of the old y is predicated by lane < nr like the
+// store.  (y is read and written, each row by the lane that owns it: no
+// __restrict__)
+template <typename T, bool NT, int B, int PB, typename TV = T>
+__global__ __launch_bounds__(256) void hspmv_slices_axpby(int32_t n_slices, uint32_t blk_order, int32_t y_nt,
+                                                          T alpha, T beta, Slices sl, XDict xd,
+                                                          const TV *__restrict__ val, const T *__restrict__ x,
+                                                          T *y) {
+  slices_body<T, NT, B, PB, TV>(n_slices, blk_order, y_nt, sl, xd, val, x, y, SliceAxpby<T>{alpha, beta});
 }
 
 }  // namespace dev

@@ -299,4 +299,16 @@ hipError_t launch_spmv(const DevCSR &A, const DevPlan &dp, int dtype, int val_dt
              : launch_typed<float, false>(A, dp, plan, (const float *)x, (float *)y, stream);
 }
 
+hipError_t launch_spmv_axpby(const DevCSR &A, const DevPlan &dp, int dtype, int val_dtype, const LaunchPlan &fwd,
+                             const AxpbyScalars &ab, const void *x, void *y, hipStream_t stream, bool reverse) {
+  if (!axpby_fusable(A, dp) || (fwd.kernel != kStream && fwd.kernel != kCsr3)) return hipErrorInvalidValue;
+  LaunchPlan plan = fwd;
+  plan.reverse = reverse;
+  if (dtype == HSPMV_F64 && val_dtype == HSPMV_F32)
+    return launch_slices_axpby_f32v64(dp, plan, ab, (const double *)x, (double *)y, stream);
+  if (dtype != val_dtype) return hipErrorInvalidValue;
+  if (dtype == HSPMV_F64) return launch_slices_axpby_f64(dp, plan, ab, (const double *)x, (double *)y, stream);
+  return launch_slices_axpby_f32(dp, plan, ab, (const float *)x, (float *)y, stream);
+}
+
 }  // namespace hspmv

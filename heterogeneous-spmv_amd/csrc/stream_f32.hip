@@ -7,4 +7,8 @@ hipError_t launch_rows_f32(const DevCSR &A, const DevPlan &dp, const LaunchPlan 
                           float *y, hipStream_t st) {
   return dev::launch_rows<float>(A, dp, p, x, y, st);
 }
+hipError_t launch_slices_axpby_f32(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                   const float *x, float *y, hipStream_t st) {
+  return dev::launch_slices<float, float>(dp, p, x, y, st, &ab);
+}
 }  // namespace hspmv

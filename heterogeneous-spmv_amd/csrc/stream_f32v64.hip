@@ -9,4 +9,8 @@ hipError_t launch_rows_f32v64(const DevCSR &A, const DevPlan &dp, const LaunchPl
                               double *y, hipStream_t st) {
   return dev::launch_rows<double, float>(A, dp, p, x, y, st);
 }
+hipError_t launch_slices_axpby_f32v64(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                      const double *x, double *y, hipStream_t st) {
+  return dev::launch_slices<double, float>(dp, p, x, y, st, &ab);
+}
 }  // namespace hspmv

@@ -7,6 +7,10 @@ hipError_t launch_rows_f64(const DevCSR &A, const DevPlan &dp, const LaunchPlan 
                           double *y, hipStream_t st) {
   return dev::launch_rows<double>(A, dp, p, x, y, st);
 }
+hipError_t launch_slices_axpby_f64(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                   const double *x, double *y, hipStream_t st) {
+  return dev::launch_slices<double, double>(dp, p, x, y, st, &ab);
+}
 }  // namespace hspmv
 
 #if (HSPMV_DIAG & (8 | 512))

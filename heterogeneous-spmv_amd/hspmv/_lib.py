@@ -145,6 +145,9 @@ SLICES_WHY = {0: "ok", 1: "off", 2: "no_dict", 3: "shape", 4: "chunked", 5: "spl
               6: "long_row", 7: "bytes", 8: "resident"}
 # hspmv_set_sweep's modes (HSPMV_SWEEP_*)
 SWEEP = {"auto": 0, "forward": 1, "alternate": 2}
+# hspmv_set_axpby_path's modes (HSPMV_AXPBY_*) and hspmv_axpby_path's answers
+AXPBY_MODES = {"auto": 0, "two_pass": 1}
+AXPBY_PATHS = {1: "two_pass", 2: "fused"}
 CSR3_PLAN_NAMES = {0: None, 1: "aligned", 2: "packed", 3: "ssr", 4: "row_groups"}
 
 
@@ -216,6 +219,11 @@ SIGNATURES = {
     "hspmv_x_device": (_P, [_H, C.c_int]),
     "hspmv_y_device": (_P, [_H, C.c_int]),
     "hspmv_spmv": (C.c_int, [_H]),
+    "hspmv_spmv_axpby": (C.c_int, [_H, C.c_double, C.c_double]),
+    "hspmv_run_axpby": (C.c_int, [_H, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Timing)]),
+    "hspmv_set_axpby_path": (C.c_int, [_H, C.c_int]),
+    "hspmv_axpby_path": (C.c_int, [_H]),
+    "hspmv_set_y": (C.c_int, [_H, _P]),
     "hspmv_synchronize": (C.c_int, [_H]),
     "hspmv_set_sweep": (C.c_int, [_H, C.c_int]),
     "hspmv_block_order": (C.c_int, [C.c_int64, C.c_int32, C.c_int, _P]),

@@ -425,6 +425,11 @@ class SpMV:
     shards keep a source index per stored entry, 4 bytes each, on the device);
     the plan, ``info`` but for ``device_bytes``, and y are those of the plain
     handle.  ``op.can_update`` tells whether ``update_values`` would be taken.
+    The general form y = alpha A x + beta y: :meth:`spmv_axpby` (with
+    :meth:`set_y` or a bound y for the old y; :meth:`run_axpby` times it) on
+    single-device handles, fused into the row-slice kernel where the plan is
+    the row slices and in two passes otherwise -- ``op.axpby_path`` tells
+    which, :meth:`set_axpby_path` forces the two passes; the same bytes.
     """
 
     def __init__(self, A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, num_gpus: int = 1,
@@ -578,6 +583,19 @@ class SpMV:
             raise ValueError(f"x has {x.shape[0]} entries, expected n={self.A.n}")
         check(lib().hspmv_set_x(self._h, _ptr(x)), "hspmv_set_x")
 
+    def set_y(self, y: np.ndarray) -> None:
+        """m values into the handle's y in use (hspmv_set_y: its own buffer, or
+        the bound array): the y_old of the next :meth:`spmv_axpby`.
+        ValueError (before any library call) for another shape than (m,) or a
+        dtype that does not cast ``same_kind`` to ``op.dtype``."""
+        y = np.asarray(y)
+        if y.shape != (self.A.m,):
+            raise ValueError(f"y has shape {y.shape}, expected (m,) = ({self.A.m},)")
+        if not np.can_cast(y.dtype, self.dtype, casting="same_kind"):
+            raise ValueError(f"y has dtype {y.dtype}, which does not cast to {np.dtype(self.dtype)}")
+        y = np.ascontiguousarray(y, dtype=self.dtype)
+        check(lib().hspmv_set_y(self._h, _ptr(y)), "hspmv_set_y")
+
     def bind_x_device(self, ptr: Optional[int]) -> None:
         check(lib().hspmv_bind_x_device(self._h, ptr), "hspmv_bind_x_device")
 
@@ -593,6 +611,38 @@ class SpMV:
     # -- compute
     def spmv(self) -> None:
         check(lib().hspmv_spmv(self._h), "hspmv_spmv")
+
+    def spmv_axpby(self, alpha: float = 1.0, beta: float = 0.0) -> None:
+        """y = alpha A x + beta y, enqueued like :meth:`spmv`
+        (hspmv_spmv_axpby): each of the two products and the sum rounded on
+        its own in ``op.dtype``; ``beta == 0`` never reads y.  Single-device
+        handles."""
+        check(lib().hspmv_spmv_axpby(self._h, float(alpha), float(beta)), "hspmv_spmv_axpby")
+
+    def run_axpby(self, alpha: float, beta: float, warmup: int = 5, iters: int = 20) -> dict:
+        """:meth:`run`'s protocol over :meth:`spmv_axpby` (hspmv_run_axpby).  y
+        evolves from call to call: keep ``|beta| < 1`` so it stays finite."""
+        t = _lib.Timing()
+        check(lib().hspmv_run_axpby(self._h, float(alpha), float(beta), int(warmup), int(iters), C.byref(t)),
+              "hspmv_run_axpby")
+        return {k: getattr(t, k) for k, _ in _lib.Timing._fields_}
+
+    @property
+    def axpby_path(self) -> str:
+        """"fused" (the row-slice kernel with the epilogue in its store) or
+        "two_pass" (the SpMV into a scratch vector, then one elementwise
+        kernel): what the next :meth:`spmv_axpby` runs (hspmv_axpby_path)."""
+        rc = lib().hspmv_axpby_path(self._h)
+        if rc < 0:
+            check(rc, "hspmv_axpby_path")
+        return _lib.AXPBY_PATHS[rc]
+
+    def set_axpby_path(self, mode: str) -> None:
+        """"auto" (fused where the plan allows it) | "two_pass"
+        (hspmv_set_axpby_path); y is the same bytes either way."""
+        if mode not in _lib.AXPBY_MODES:
+            raise ValueError(f"axpby path {mode!r} (one of {', '.join(_lib.AXPBY_MODES)})")
+        check(lib().hspmv_set_axpby_path(self._h, _lib.AXPBY_MODES[mode]), "hspmv_set_axpby_path")
 
     def synchronize(self) -> None:
         check(lib().hspmv_synchronize(self._h), "hspmv_synchronize")

@@ -56,7 +56,9 @@ extern "C" {
  * hspmv_values_fit_f32, hspmv_slices_plan_vec; new values for a planned
  * handle or operator: hspmv_update_values, hspmv_mm_update_values,
  * HSPMV_VALUES_DEVICE, and for column-sorted handles hspmv_create_updatable,
- * hspmv_can_update_values -- functions only, no struct grew. */
+ * hspmv_can_update_values; the general form y = alpha A x + beta y:
+ * hspmv_spmv_axpby, hspmv_run_axpby, hspmv_set_y, hspmv_set_axpby_path,
+ * hspmv_axpby_path -- functions only, no struct grew. */
 
 /* ---------------------------------------------------------------- status */
 #define HSPMV_OK 0
@@ -566,6 +568,60 @@ void *hspmv_y_device(hspmv_handle *h, int gpu);
 int hspmv_spmv(hspmv_handle *h);
 int hspmv_synchronize(hspmv_handle *h);
 
+/* Enqueue ONE y = alpha*A*x + beta*y on the handle's stream: the general form
+ * a residual (r = b - A x: alpha = -1, beta = 1 over y = b), a Newton or time
+ * step and a CG-shaped loop need, without the spare vector and the separate
+ * update they otherwise run after hspmv_spmv.
+ *
+ * Contract.  For every row r, with T the handle's vector dtype
+ * (hspmv_get_dtypes; double for a mixed handle) and alpha_T, beta_T the two
+ * scalars converted to T once, on the host:
+ *     s    = the bits hspmv_spmv would write to y[r] for this handle, plan and x
+ *     y[r] = fl( fl(alpha_T * s) + fl(beta_T * y_old[r]) )    if beta_T != 0
+ *     y[r] = fl(alpha_T * s)                                  if beta_T == 0
+ * Each operation is rounded on its own, no fma.  beta_T == 0 never reads
+ * y_old, so a NaN or Inf there does not propagate (beta == 0 always converts
+ * to 0; so does a double too small for an fp32 handle).  alpha = 1, beta = 0
+ * gives hspmv_spmv's bytes.  There is no other shortcut: alpha == 0 still
+ * forms s, so a NaN of A x shows.  y_old is what the handle's y holds at the
+ * call: its own buffer (hspmv_set_y fills it) or the array bound by
+ * hspmv_bind_y_device.  The call is enqueued with no host synchronisation and
+ * advances the sweep phase exactly as hspmv_spmv does: a handle that
+ * alternates its sweep keeps alternating across mixed hspmv_spmv and
+ * hspmv_spmv_axpby calls.
+ *
+ * Two paths, the same bytes.  A handle whose plan is the row slices
+ * (hspmv_info.row_slices) runs one kernel, the slice kernel with the epilogue
+ * in place of its store (fused: one extra pass over m elements, the read of
+ * y_old).  Every other plan runs hspmv_spmv's launches into a scratch vector
+ * of m elements the handle owns, then one elementwise kernel (two-pass).  The
+ * scratch is allocated by the first two-pass call (the only call that
+ * allocates), freed with the handle and counted in hspmv_info.device_bytes
+ * from then on.  hspmv_set_axpby_path(h, HSPMV_AXPBY_TWO_PASS) forces the
+ * two-pass path (HSPMV_AXPBY_AUTO, the default: fused where it can run; other
+ * modes HSPMV_E_INVALID); hspmv_axpby_path returns the path the next call
+ * takes, HSPMV_AXPBY_PATH_TWO_PASS or HSPMV_AXPBY_PATH_FUSED.
+ *
+ * HSPMV_E_INVALID, decided before anything is launched, y untouched: a NULL
+ * handle; a sharded handle (more than one shard, repeated devices included --
+ * hspmv_set_y, hspmv_run_axpby and hspmv_axpby_path refuse it too); x and y
+ * the same device pointer.  HSPMV_E_STATE: x not set.
+ *
+ * Not covered: sharded handles; hspmv_mm_*; the epilogue inside the chunked,
+ * vector and column-sorted kernels (they take the two-pass path); a fused dot
+ * product. */
+#define HSPMV_AXPBY_AUTO 0
+#define HSPMV_AXPBY_TWO_PASS 1
+#define HSPMV_AXPBY_PATH_TWO_PASS 1
+#define HSPMV_AXPBY_PATH_FUSED 2
+int hspmv_spmv_axpby(hspmv_handle *h, double alpha, double beta);
+int hspmv_set_axpby_path(hspmv_handle *h, int mode);
+int hspmv_axpby_path(hspmv_handle *h);
+/* y (m entries of the vector dtype) from host memory into the handle's y in
+ * use -- its own buffer, or the array bound by hspmv_bind_y_device -- as
+ * hspmv_set_x does for x: consumed before return.  Single-device handles. */
+int hspmv_set_y(hspmv_handle *h, const void *y_host);
+
 /* Sweep direction of the STREAM / CSR3 row kernel (the row-slice kernel
  * included) from one SpMV of this handle to the next.  A matrix larger than
  * the 256 MiB Infinity Cache that is swept first block to last on every call
@@ -598,6 +654,12 @@ int hspmv_block_order(int64_t n_blocks, int32_t xcd_chunk, int reverse, int32_t 
 /* Reference timing protocol: warmup SpMVs, then iters timed SpMVs, each
  * bracketed by events + synchronize (hip/spmv-auto-mi100.cu:214-236). */
 int hspmv_run(hspmv_handle *h, int warmup, int iters, hspmv_timing *out);
+/* hspmv_run's protocol over hspmv_spmv_axpby(h, alpha, beta), with its
+ * refusals.  y is not reset between iterations: it evolves from call to call
+ * (y_k+1 = alpha A x + beta y_k), so the caller keeps |beta| < 1 for it to
+ * stay finite over warmup + iters calls.  gflops = 2 nnz / t_min; gbps_alg
+ * counts hspmv_alg_bytes plus, for beta != 0, the m elements of y_old read. */
+int hspmv_run_axpby(hspmv_handle *h, double alpha, double beta, int warmup, int iters, hspmv_timing *out);
 
 /* y (m entries of dtype) -> host; gathers the shards of a multi-GPU handle
  * (getY, csrk.cu:110-113). */
