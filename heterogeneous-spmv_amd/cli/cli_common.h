@@ -65,6 +65,16 @@
 //                       / "AxpbyTimeAvg:" (wall) and "AxpbyKernelMin:" (not
 //                       with --rhs or --gpus > 1; keep |BETA| < 1: y evolves
 //                       over the timed calls)
+//   --dot               after --axpby's part (ALPHA,BETA as given there, else
+//                       1,0): y0 as for --axpby, w = the --x generator with
+//                       seed SEED + 2; one hspmv_spmv_axpby_dot(ALPHA, BETA)
+//                       asking for both dots, checked against long-double host
+//                       sums over the device's own y within (m + 4) 2^-53
+//                       sum |terms| ("DotCheck: PASS|FAIL wy=... yy=...
+//                       path=fused|two_pass"); then hspmv_run_axpby_dot is
+//                       timed from y0: "DotTimeMin:" / "DotTimeMax:" /
+//                       "DotTimeAvg:" (wall), "DotKernelMin:" (not with --rhs
+//                       or --gpus > 1)
 //   --dump-y PATH       write y as raw binary (dtype) for external checks
 //   --no-check          skip the serial CPU check
 #pragma once
@@ -98,6 +108,7 @@ struct Options {
   int update_values = 0;  // > 0: rounds of hspmv_update_values after the timed loop
   bool axpby = false;     // --axpby ALPHA,BETA: hspmv_spmv_axpby checked, hspmv_run_axpby timed
   double alpha = 1.0, beta = 0.0;
+  bool dot = false;       // --dot: hspmv_spmv_axpby_dot(ALPHA, BETA) checked, hspmv_run_axpby_dot timed
   std::string dump_y;
   std::string params = "mi355x";
   bool bandk = true;  // spmv-csrk on a .csr: band-k reorder (the reference's CSRk_Graph)
@@ -183,6 +194,8 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
       o.beta = strtod(b, &end);
       if (end == b || *end != '\0') { fprintf(stderr, "bad --axpby %s (ALPHA,BETA)\n", v); return false; }
       o.axpby = true;
+    } else if (a == "--dot") {
+      o.dot = true;
     } else if (a == "--no-check") {
       o.check = false;
     } else if (a == "--dump-y") {
@@ -207,9 +220,14 @@ inline bool parse_options(int argc, char **argv, int first, Options &o) {
     }
     if (o.update_values > 0) { fprintf(stderr, "--rhs takes no --update-values\n"); return false; }
     if (o.axpby) { fprintf(stderr, "--rhs takes no --axpby\n"); return false; }
+    if (o.dot) { fprintf(stderr, "--rhs takes no --dot\n"); return false; }
   }
   if (o.axpby && o.gpus != 1) {
     fprintf(stderr, "--axpby runs on one GPU (not --gpus %d)\n", o.gpus);
+    return false;
+  }
+  if (o.dot && o.gpus != 1) {
+    fprintf(stderr, "--dot runs on one GPU (not --gpus %d)\n", o.gpus);
     return false;
   }
   return true;
@@ -399,6 +417,61 @@ int run_axpby(hspmv_handle *h, int64_t m, const void *s_bytes, int num_runs, con
   return differ ? 2 : 0;
 }
 
+// --dot: one hspmv_spmv_axpby_dot(ALPHA, BETA, both dots) over y0 (as for
+// --axpby) with w the --x generator at seed SEED + 2; the two results against
+// long-double host sums over the device's own y, within (m + 4) 2^-53
+// sum |terms| (any order of m double sums over products rounded once), then
+// hspmv_run_axpby_dot from y0.  Returns 0, 2 for a failed check, 1 after a
+// library error.
+template <typename T>
+int run_dot(hspmv_handle *h, int64_t m, int num_runs, const Options &o, const int32_t *perm) {
+  Options oy = o, ow = o;
+  oy.seed = o.seed + 1;
+  ow.seed = o.seed + 2;
+  std::vector<double> y64, w64;
+  fill_x(oy, m, y64);
+  fill_x(ow, m, w64);
+  std::vector<T> y0((size_t)(m ? m : 1)), w(y0.size()), got(y0.size());
+  for (int64_t i = 0; i < m; ++i) {
+    y0[(size_t)i] = (T)y64[(size_t)(perm ? perm[i] : i)];
+    w[(size_t)i] = (T)w64[(size_t)(perm ? perm[i] : i)];
+  }
+  const int path = hspmv_axpby_path(h);
+  if (path < 0) return die("hspmv_axpby_path");
+  const unsigned both = HSPMV_DOT_WY | HSPMV_DOT_YY;
+  double d[2] = {0.0, 0.0};
+  if (hspmv_set_y(h, y0.data()) != HSPMV_OK) return die("hspmv_set_y");
+  if (hspmv_set_w(h, w.data()) != HSPMV_OK) return die("hspmv_set_w");
+  if (hspmv_spmv_axpby_dot(h, o.alpha, o.beta, both) != HSPMV_OK) return die("hspmv_spmv_axpby_dot");
+  if (hspmv_get_dots(h, d) != HSPMV_OK) return die("hspmv_get_dots");
+  if (hspmv_get_y(h, got.data()) != HSPMV_OK) return die("hspmv_get_y");
+  long double ref[2] = {0.0L, 0.0L}, mag[2] = {0.0L, 0.0L};
+  for (int64_t i = 0; i < m; ++i) {
+    const long double yv = (long double)got[(size_t)i];
+    const long double t0 = (long double)w[(size_t)i] * yv, t1 = yv * yv;
+    ref[0] += t0;
+    ref[1] += t1;
+    mag[0] += fabsl(t0);
+    mag[1] += t1;
+  }
+  bool pass = true;
+  for (int k = 0; k < 2; ++k) {
+    const long double bound = (long double)(m + 4) * ldexpl(1.0L, -53) * mag[k];
+    if (!(fabsl((long double)d[k] - ref[k]) <= bound)) pass = false;
+  }
+  printf("DotCheck: %s wy=%.17g yy=%.17g path=%s\n", pass ? "PASS" : "FAIL", d[0], d[1],
+         path == HSPMV_AXPBY_PATH_FUSED ? "fused" : "two_pass");
+  if (hspmv_set_y(h, y0.data()) != HSPMV_OK) return die("hspmv_set_y");
+  hspmv_timing t;
+  if (hspmv_run_axpby_dot(h, o.alpha, o.beta, both, 5, num_runs, &t) != HSPMV_OK)
+    return die("hspmv_run_axpby_dot");
+  printf("DotTimeMin: %lg\n", t.wall_min);
+  printf("DotTimeMax: %lg\n", t.wall_max);
+  printf("DotTimeAvg: %lg\n", t.wall_avg);
+  printf("DotKernelMin: %lg\n", t.t_min);
+  return pass ? 0 : 2;
+}
+
 // Runs the timed protocol on an already-read matrix and prints the report.
 // perm (optional, m entries): A is the band-k permutation of the file's
 // matrix, row i = file row perm[i]; x is generated in file order and
@@ -521,6 +594,12 @@ inline int run_and_report(const hspmv_csr_buf &A, const hspmv_csr3_buf *maps, in
                                      : run_axpby<float>(h, A.m, y.data(), num_runs, o, perm);
     if (arc == 1) return 1;
     if (arc) rc = arc;
+  }
+  if (o.dot) {
+    const int drc = vdt == HSPMV_F64 ? run_dot<double>(h, A.m, num_runs, o, perm)
+                                     : run_dot<float>(h, A.m, num_runs, o, perm);
+    if (drc == 1) return 1;
+    if (drc) rc = drc;
   }
   if (o.update_values > 0) {
     // new values on the planned handle, N rounds: round k holds the file's

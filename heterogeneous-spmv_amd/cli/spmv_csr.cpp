@@ -10,7 +10,7 @@ int main(int argc, char **argv) {
   if (argc < 3) {
     printf("%s inputfile.csr num_runs [--gpus N] [--dtype f32|f64] [--vector-dtype f32|f64] [--x ones|rand:SEED] "
            "[--kernel auto|stream|vector[:L]] [--nt] [--sweep forward|alternate] [--rhs K] "
-           "[--update-values N] [--axpby ALPHA,BETA] [--dump-y PATH] [--no-check]\n",
+           "[--update-values N] [--axpby ALPHA,BETA] [--dot] [--dump-y PATH] [--no-check]\n",
            argv[0]);
     return 0;
   }

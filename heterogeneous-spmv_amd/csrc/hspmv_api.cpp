@@ -170,6 +170,67 @@ int enqueue_axpby(hspmv_handle *h, const AxpbyScalars &ab) {
   return HSPMV_OK;
 }
 
+// ---- ... and w . y, y . y from the same pass (hspmv_spmv_axpby_dot)
+
+int check_dot_which(unsigned which) {
+  if (which == 0 || (which & ~(HSPMV_DOT_WY | HSPMV_DOT_YY)))
+    return set_error(HSPMV_E_INVALID, "which = 0x%x (HSPMV_DOT_WY, HSPMV_DOT_YY or both)", which);
+  return HSPMV_OK;
+}
+
+// prepare_axpby, the dot call's own refusals, and the buffers this call needs
+// that the shard does not have yet: the partial pairs (both paths' share in
+// one allocation, so a change of path allocates nothing) and the own result.
+int prepare_axpby_dot(hspmv_handle *h, const char *what, unsigned which) {
+  int rc;
+  if ((rc = check_dot_which(which))) return rc;
+  if ((rc = check_single_shard(h, what))) return rc;
+  Shard &s = h->shards[0];
+  DevDot &d = s.dot;
+  if (which & HSPMV_DOT_WY) {
+    if (!d.w) return set_error(HSPMV_E_STATE, "%s: HSPMV_DOT_WY with no w (hspmv_set_w / hspmv_bind_w_device)", what);
+    if (d.w == s.y && h->m > 0)
+      return set_error(HSPMV_E_INVALID, "%s: w and y are the same device array (ask for HSPMV_DOT_YY)", what);
+  }
+  if ((rc = prepare_axpby(h, what))) return rc;
+  if (!d.d_part) {
+    d.n_fused = axpby_fusable(s.A, s.dp) ? s.dp.sl.n : 0;
+    d.n_2p = axpby_dot_blocks(h->m);
+    const size_t bytes = 16 * (size_t)(d.n_fused + d.n_2p);
+    if ((rc = s.dev.alloc(&d.d_part, bytes))) return rc;
+    // (a wave task without rows never writes its pair: it stays 0.0)
+    if (bytes) HIP_TRY(hipMemsetAsync(d.d_part, 0, bytes, s.dev.stream));
+  }
+  if (!d.out && !d.d_out && (rc = s.dev.alloc(&d.d_out, 2 * sizeof(double)))) return rc;
+  return HSPMV_OK;
+}
+
+// enqueue_axpby with the dots (prepare_axpby_dot has passed): the path's
+// kernel(s), then the finish kernel over the partials that path wrote.
+int enqueue_axpby_dot(hspmv_handle *h, const AxpbyScalars &ab, unsigned which) {
+  Shard &s = h->shards[0];
+  DevDot &d = s.dot;
+  double *out = d.out ? d.out : d.d_out;
+  DotArgs da{(which & HSPMV_DOT_WY) ? d.w : nullptr, (which & HSPMV_DOT_YY) != 0, d.d_part};
+  int64_t n = 0;
+  hipError_t e;
+  if (axpby_fused(h)) {
+    n = d.n_fused;
+    e = launch_spmv_axpby_dot(s.A, s.dp, h->dtype, h->val_dtype, s.plan, ab, da, s.x, s.y, s.dev.stream,
+                              shard_reverse(h, s));
+  } else {
+    if (int rc = launch_shard(h, s, s.d_axpby)) return rc;
+    da.partials = d.d_part + 2 * d.n_fused;
+    e = launch_axpby_dot(h->dtype, h->m, ab, s.plan.y_nt, s.d_axpby, s.y, da, &n, s.dev.stream);
+  }
+  if (e == hipSuccess) e = launch_dot_finish(da.partials, n, out, s.dev.stream);
+  if (e != hipSuccess)
+    return set_error(HSPMV_E_HIP, "axpby_dot launch on GPU %d failed: %s", s.dev.device, hipGetErrorString(e));
+  d.last = out;
+  h->sweep_phase = !h->sweep_phase;
+  return HSPMV_OK;
+}
+
 int check_devices(const int *devices, int n, int *ndev_out) {
   int rc;
   if ((rc = check_device(0, ndev_out))) return rc;  // any device at all, and how many
@@ -458,6 +519,86 @@ int hspmv_run_axpby(hspmv_handle *h, double alpha, double beta, int warmup, int 
   out->gflops = tmin > 0 ? 2.0 * (double)h->nnz / tmin * 1e-9 : 0.0;
   out->gbps_alg = tmin > 0 ? bytes / tmin * 1e-9 : 0.0;
   out->num_gpus = 1;
+  return HSPMV_OK;
+}
+
+int hspmv_spmv_axpby_dot(hspmv_handle *h, double alpha, double beta, unsigned which) {
+  int rc;
+  if ((rc = prepare_axpby_dot(h, "hspmv_spmv_axpby_dot", which))) return rc;
+  return enqueue_axpby_dot(h, AxpbyScalars{alpha, beta}, which);
+}
+
+int hspmv_run_axpby_dot(hspmv_handle *h, double alpha, double beta, unsigned which, int warmup, int iters,
+                        hspmv_timing *out) {
+  clear_error();
+  int rc;
+  if ((rc = check_dot_which(which))) return rc;
+  if ((rc = check_single_shard(h, "hspmv_run_axpby_dot"))) return rc;
+  if (!out || iters < 1 || warmup < 0) return set_error(HSPMV_E_INVALID, "bad arguments");
+  if ((rc = prepare_axpby_dot(h, "hspmv_run_axpby_dot", which))) return rc;
+  const AxpbyScalars ab{alpha, beta};
+  std::vector<DevCtx *> devs{&h->shards[0].dev};
+  if ((rc = timed_run(devs, warmup, iters, [&](size_t) { return enqueue_axpby_dot(h, ab, which); }, out)))
+    return rc;
+  const double tmin = out->t_min;
+  // hspmv_run_axpby's bytes plus the one pass over w
+  const double sv = (double)dtype_size(h->dtype);
+  const double bytes = alg_bytes_of(h->m, h->x_entries(), h->nnz, h->dtype, h->val_dtype, h->n_ssr, h->n_sr) +
+                       ((beta != 0.0) ? sv * (double)h->m : 0.0) +
+                       ((which & HSPMV_DOT_WY) ? sv * (double)h->m : 0.0);
+  out->gflops = tmin > 0 ? 2.0 * (double)h->nnz / tmin * 1e-9 : 0.0;
+  out->gbps_alg = tmin > 0 ? bytes / tmin * 1e-9 : 0.0;
+  out->num_gpus = 1;
+  return HSPMV_OK;
+}
+
+int hspmv_set_w(hspmv_handle *h, const void *w_host) {
+  clear_error();
+  int rc;
+  if ((rc = check_single_shard(h, "hspmv_set_w"))) return rc;
+  if (!w_host && h->m > 0) return set_error(HSPMV_E_INVALID, "w is NULL");
+  Shard &s = h->shards[0];
+  const size_t bytes = dtype_size(h->dtype) * (size_t)h->m;
+  HIP_TRY(hipSetDevice(s.dev.device));
+  if (!s.dot.d_w && (rc = s.dev.alloc(&s.dot.d_w, bytes))) return rc;
+  if (bytes) {
+    HIP_TRY(hipMemcpyAsync(s.dot.d_w, w_host, bytes, hipMemcpyHostToDevice, s.dev.stream));
+    HIP_TRY(hipStreamSynchronize(s.dev.stream));
+  }
+  s.dot.w = s.dot.d_w;
+  return HSPMV_OK;
+}
+
+int hspmv_bind_w_device(hspmv_handle *h, const void *w_dev) {
+  clear_error();
+  int rc;
+  if ((rc = check_single_shard(h, "hspmv_bind_w_device"))) return rc;
+  DevDot &d = h->shards[0].dot;
+  d.w = w_dev ? w_dev : d.d_w;  // (no own w yet: none in use)
+  return HSPMV_OK;
+}
+
+int hspmv_bind_dots_device(hspmv_handle *h, double *dots_dev) {
+  clear_error();
+  int rc;
+  if ((rc = check_single_shard(h, "hspmv_bind_dots_device"))) return rc;
+  if (reinterpret_cast<uintptr_t>(dots_dev) % 8 != 0)
+    return set_error(HSPMV_E_INVALID, "hspmv_bind_dots_device: the two doubles must be 8-byte aligned");
+  h->shards[0].dot.out = dots_dev;
+  return HSPMV_OK;
+}
+
+int hspmv_get_dots(hspmv_handle *h, double out[2]) {
+  clear_error();
+  int rc;
+  if ((rc = check_single_shard(h, "hspmv_get_dots"))) return rc;
+  if (!out) return set_error(HSPMV_E_INVALID, "NULL output");
+  Shard &s = h->shards[0];
+  if (!s.dot.last)
+    return set_error(HSPMV_E_STATE, "hspmv_get_dots before any hspmv_spmv_axpby_dot on this handle");
+  HIP_TRY(hipSetDevice(s.dev.device));
+  HIP_TRY(hipMemcpyAsync(out, s.dot.last, 2 * sizeof(double), hipMemcpyDeviceToHost, s.dev.stream));
+  HIP_TRY(hipStreamSynchronize(s.dev.stream));
   return HSPMV_OK;
 }
 

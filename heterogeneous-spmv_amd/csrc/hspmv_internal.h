@@ -430,6 +430,49 @@ hipError_t launch_spmv_axpby(const DevCSR &A, const DevPlan &dp, int dtype, int 
 hipError_t launch_axpby(int dtype, int64_t m, const AxpbyScalars &ab, bool y_nt, const void *s, void *y,
                         hipStream_t stream);
 
+// ---- w . y and y . y from the pass that writes y (hspmv_spmv_axpby_dot,
+// DESIGN.md §5f).  What one launch reads and writes beside y:
+struct DotArgs {
+  const void *w;     // m entries of the vector dtype; nullptr: w . y not asked for (never read)
+  bool yy;           // y . y asked for
+  double *partials;  // {wy, yy} pairs, 16-byte aligned: one per slice (fused) / per workgroup (two-pass)
+};
+// A shard's three buffers of the dot calls (Shard::dot), each allocated
+// through its DevCtx by the first call that needs it and freed with it.
+// partials: n_fused pairs for the slice kernel (one per wave task, zeroed
+// once: a task without rows never writes its pair), then n_2p pairs for the
+// two-pass kernel's workgroups.
+struct DevDot {
+  void *d_w = nullptr;         // own w (m entries; hspmv_set_w)
+  const void *w = nullptr;     // w in use (own or bound); nullptr: none yet
+  double *d_part = nullptr;
+  int64_t n_fused = 0, n_2p = 0;
+  double *d_out = nullptr;     // own {wy, yy}
+  double *out = nullptr;       // bound results (hspmv_bind_dots_device); nullptr: d_out
+  double *last = nullptr;      // where the last dot call wrote (hspmv_get_dots); nullptr: no call yet
+};
+// Workgroups hspmv_axpby_dot runs for m rows at most (its partials).
+inline int64_t axpby_dot_blocks(int64_t m) { return (m + 255) / 256; }
+// The fused path's kernel: launch_spmv_axpby with hspmv_slices_axpby_dot;
+// dot.partials holds dp.sl.n pairs.
+hipError_t launch_slices_axpby_dot_f32(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                       const DotArgs &dot, const float *x, float *y, hipStream_t st);
+hipError_t launch_slices_axpby_dot_f64(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                       const DotArgs &dot, const double *x, double *y, hipStream_t st);
+hipError_t launch_slices_axpby_dot_f32v64(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                          const DotArgs &dot, const double *x, double *y, hipStream_t st);
+hipError_t launch_spmv_axpby_dot(const DevCSR &A, const DevPlan &dp, int dtype, int val_dtype,
+                                 const LaunchPlan &plan, const AxpbyScalars &ab, const DotArgs &dot, const void *x,
+                                 void *y, hipStream_t stream, bool reverse = false);
+// The two-pass path's second pass (axpby.hip): launch_axpby's update and
+// stores, and each workgroup's pair into dot.partials[block] (at most
+// axpby_dot_blocks(m) of them); *n_partials: how many it wrote.
+hipError_t launch_axpby_dot(int dtype, int64_t m, const AxpbyScalars &ab, bool y_nt, const void *s, void *y,
+                            const DotArgs &dot, int64_t *n_partials, hipStream_t stream);
+// Both paths' last launch: out[0..1] (8-byte aligned) = the sums of the n
+// pairs, in an order that depends on n alone (one workgroup of 1024 threads).
+hipError_t launch_dot_finish(const double *partials, int64_t n, double *out, hipStream_t stream);
+
 // ---- value refresh (refresh.hip; hspmv_update_values, hspmv_update.cpp):
 // the derived copies of the values rebuilt on the device from src, the new
 // values in the shard's CSR order (val_dtype: the stored values').  Both

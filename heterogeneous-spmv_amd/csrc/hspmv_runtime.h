@@ -181,6 +181,7 @@ struct Shard {
   void *d_y = nullptr;     // own y (m_shard entries) -- or a view into d_yfull
   void *d_yfull = nullptr; // multi-GPU: padded all-gather buffer P*max_rows
   void *d_axpby = nullptr; // hspmv_spmv_axpby's two-pass scratch (m entries; from the first such call on)
+  DevDot dot;              // hspmv_spmv_axpby_dot's w, partials and results (each from the first call that needs it)
   const void *x = nullptr; // x in use (own or bound)
   void *y = nullptr;       // y in use (own or bound)
   int64_t x_entries = 0;   // distinct columns of this shard

@@ -5,7 +5,7 @@
 //
 // The variants of one unit, per NT in {0, 1} and U in {2, 3, 4, 5, 6, 8, 16}
 // (90 kernels, 36 of them with prefetch), plus the 4 slice kernels (and their
-// 4 hspmv_slices_axpby twins, launch_slices):
+// 4 hspmv_slices_axpby and 4 hspmv_slices_axpby_dot twins, launch_slices):
 //   column format   STREAM                               CSR3
 //   32-bit, col16   W in {1, 2, 4} x windows on / off    W in {1, 2, 4, 8}, and
 //   modes 1 and 2   x padded on / off (no padding with   W = 4 with x windows
@@ -28,21 +28,29 @@ inline uint32_t block_order(const LaunchPlan &p) {
 }
 
 // ab: nullptr runs hspmv_slices (y = A x); else hspmv_slices_axpby with the
-// two scalars converted to T here, once (y = alpha (A x) + beta y).
+// two scalars converted to T here, once (y = alpha (A x) + beta y); with dot
+// as well, hspmv_slices_axpby_dot (dot->partials: dp.sl.n pairs).
 template <typename T, typename TV>
 hipError_t launch_slices(const DevPlan &dp, const LaunchPlan &p, const T *x, T *y, hipStream_t st,
-                         const AxpbyScalars *ab = nullptr) {
+                         const AxpbyScalars *ab = nullptr, const DotArgs *dot = nullptr) {
   if (!dp.xd.blk || !dp.sl.len || !dp.sl.pos || !dp.sl.val || p.waves_per_block != 4 ||
       p.blocks != ((int64_t)dp.sl.n + 3) / 4 ||
       !(dp.sl.pos_bits == 16 || (dp.sl.pos_bits == 12 && dp.sl.ppre)))
     return hipErrorInvalidValue;  // the host built the slices for another block shape
+  if (dot && (!ab || !dot->partials || reinterpret_cast<uintptr_t>(dot->partials) % 16 != 0))
+    return hipErrorInvalidValue;
   const Slices sl{dp.sl.desc, dp.sl.len, dp.sl.pos, dp.sl.ppre};
   const XDict xd{dp.xd.blk, reinterpret_cast<const int2 *>(dp.xd.runs)};
   const unsigned dyn = (unsigned)dp.xd.lds_bytes + (unsigned)p.dyn_lds;
   const TV *val = static_cast<const TV *>(dp.sl.val);
   static_switch<12, 16>(dp.sl.pos_bits, [&](auto PB) {
     static_flag(p.nontemporal, [&](auto NT) {
-      if (ab)
+      if (dot)
+        hipLaunchKernelGGL((hspmv_slices_axpby_dot<T, NT, HSPMV_SLICE_BATCH, PB, TV>), dim3((unsigned)p.blocks),
+                           dim3(256), dyn, st, dp.sl.n, block_order(p), (int32_t)p.y_nt, (T)ab->alpha, (T)ab->beta,
+                           (uint32_t)dot->yy, static_cast<const T *>(dot->w),
+                           reinterpret_cast<sl_d2 *>(dot->partials), sl, xd, val, x, y);
+      else if (ab)
         hipLaunchKernelGGL((hspmv_slices_axpby<T, NT, HSPMV_SLICE_BATCH, PB, TV>), dim3((unsigned)p.blocks),
                            dim3(256), dyn, st, dp.sl.n, block_order(p), (int32_t)p.y_nt, (T)ab->alpha, (T)ab->beta,
                            sl, xd, val, x, y);

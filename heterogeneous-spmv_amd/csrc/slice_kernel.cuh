@@ -1,7 +1,8 @@
 // slice_kernel.cuh -- hspmv_slices, the lane-per-row kernel of dictionary
 // handles with row slices (STREAM / CSR3 handles; instantiated beside the row
-// kernels, row_launch.cuh), and hspmv_slices_axpby, its twin whose store is
-// the y = alpha (A x) + beta y epilogue.  Device code only.
+// kernels, row_launch.cuh), hspmv_slices_axpby, its twin whose store is the
+// y = alpha (A x) + beta y epilogue, and hspmv_slices_axpby_dot, which also
+// sums w . y and y . y over the values it stores.  Device code only.
 //
 // The transposed (sliced-ELL) shape of the dictionary kernels, for handles
 // whose every row is summed serially anyway (hspmv_slices.cpp holds the
@@ -175,10 +176,15 @@ __device__ __forceinline__ T slice_consume(T acc, const SliceBatch<TV, B> &q, co
 
 // What a slice kernel does with a row's sum before it is stored.  `before`
 // runs ahead of the slot loop, for the lanes that own a row, and what it
-// returns is handed to `after` with the sum.
+// returns is handed to `after` with the sum.  A policy with kTerms (only
+// SliceAxpbyDot) also has `terms`, which takes the stored value on the same
+// lanes, and `reduce`, which runs on every lane of a wave that has rows with
+// what `terms` left; without kTerms neither is compiled.
 // hspmv_slices: the sum as it is.
 template <typename T>
 struct SliceStoreSum {
+  static constexpr bool kTerms = false;
+  struct Terms {};
   struct Old {};
   __device__ __forceinline__ Old before(const T *, int32_t) const { return Old{}; }
   __device__ __forceinline__ T after(T acc, Old) const { return acc; }
@@ -196,6 +202,8 @@ struct SliceStoreSum {
 // -- a kernel-uniform branch that issues no load of y.
 template <typename T>
 struct SliceAxpby {
+  static constexpr bool kTerms = false;
+  struct Terms {};
   T alpha, beta;
   struct Old {
     const T *p;
@@ -215,13 +223,54 @@ struct SliceAxpby {
   }
 };
 
+// hspmv_slices_axpby_dot: SliceAxpby's store, then the
+// slice's share of w . y and y . y over the values just stored, in double
+// whatever T is.  w: nullptr when w . y is not asked for (kernel-uniform, no
+// load then); its load sits beside the old y's, ahead of the slot loop.  A
+// lane that owns no row keeps both terms at 0.0.  One wave_sum_dpp per term
+// (a fixed order), and lane 0 stores the pair to partials[t], t the logical
+// slice: the sweep direction moves no partial.
+typedef double sl_d2 __attribute__((ext_vector_type(2)));
+template <typename T>
+struct SliceAxpbyDot {
+  static constexpr bool kTerms = true;
+  SliceAxpby<T> ab;
+  const T *w;
+  uint32_t yy;  // y . y asked for
+  sl_d2 *partials;
+  struct Old {
+    typename SliceAxpby<T>::Old o;
+    T wv;
+  };
+  struct Terms {
+    double wy = 0.0, yy = 0.0;
+  };
+  __device__ __forceinline__ Old before(const T *y, int32_t row) const {
+    Old q{ab.before(y, row), T(0)};
+    if (w) q.wv = w[row];
+    return q;
+  }
+  __device__ __forceinline__ T after(T acc, const Old &q) const { return ab.after(acc, q.o); }
+  __device__ __forceinline__ void terms(Terms &tm, T out, const Old &q) const {
+    const double yd = (double)out;
+    if (w) tm.wy = (double)q.wv * yd;
+    if (yy) tm.yy = yd * yd;
+  }
+  __device__ __forceinline__ void reduce(const Terms &tm, int64_t t, int lane) const {
+    const double a = wave_sum_dpp<double>(tm.wy);
+    const double b = wave_sum_dpp<double>(tm.yy);
+    if (lane == 0) partials[t] = sl_d2{a, b};
+  }
+};
+
 // One workgroup = one dictionary block (four wave tasks, or a half block's
 // two and two empty ones), staged by stage_xdict exactly as in the chunked
 // kernels.  Each wave reads its slice's descriptor (one scalar load) and its
 // rows' lengths before the staging; after the barrier it walks the slot
 // columns in batches of B, the next batch's loads issued before the current
 // one is consumed.  LDS: the dictionary alone.  Same bits as the row kernels.
-// The body of both kernels below: EP is SliceStoreSum or SliceAxpby.
+// The body of the kernels below: EP is SliceStoreSum, SliceAxpby or
+// SliceAxpbyDot.
 template <typename T, bool NT, int B, int PB, typename TV, typename EP>
 __device__ __forceinline__ void slices_body(int32_t n_slices, uint32_t blk_order, int32_t y_nt, const Slices &sl,
                                             const XDict &xd, const TV *__restrict__ val,
@@ -284,12 +333,18 @@ __device__ __forceinline__ void slices_body(int32_t n_slices, uint32_t blk_order
   // y[r0 + lane], and either form alone compiles to other registers here)
   if constexpr (diag(kDiagNoStore)) {  // ablation: no y stores (kept live)
     if (lane < nr && acc == T(12345.678)) y[r0 + lane] = acc;
-  } else if (lane < nr) {
-    const T out = ep.after(acc, old);
-    if (y_nt)
-      __builtin_nontemporal_store(out, y + r0 + lane);
-    else
-      y[r0 + lane] = out;
+  } else {
+    [[maybe_unused]] typename EP::Terms tm;
+    if (lane < nr) {
+      const T out = ep.after(acc, old);
+      if (y_nt)
+        __builtin_nontemporal_store(out, y + r0 + lane);
+      else
+        y[r0 + lane] = out;
+      if constexpr (EP::kTerms) ep.terms(tm, out, old);
+    }
+    // every lane of the wave: the idle ones bring 0.0
+    if constexpr (EP::kTerms) ep.reduce(tm, t, lane);
   }
 }
 
@@ -312,6 +367,20 @@ __global__ __launch_bounds__(256) void hspmv_slices_axpby(int32_t n_slices, uint
                                                           const TV *__restrict__ val, const T *__restrict__ x,
                                                           T *y) {
   slices_body<T, NT, B, PB, TV>(n_slices, blk_order, y_nt, sl, xd, val, x, y, SliceAxpby<T>{alpha, beta});
+}
+
+// hspmv_slices_axpby and, from the values it stores, the slice's pair
+// {sum w[r] y[r], sum y[r]^2} in double into partials[t] (n_slices pairs;
+// hspmv_spmv_axpby_dot's fused path, finished by hspmv_dot_finish).  A wave
+// without rows returns before it and writes no pair.
+template <typename T, bool NT, int B, int PB, typename TV = T>
+__global__ __launch_bounds__(256) void hspmv_slices_axpby_dot(int32_t n_slices, uint32_t blk_order, int32_t y_nt,
+                                                              T alpha, T beta, uint32_t yy, const T *w,
+                                                              sl_d2 *__restrict__ partials, Slices sl, XDict xd,
+                                                              const TV *__restrict__ val,
+                                                              const T *__restrict__ x, T *y) {
+  slices_body<T, NT, B, PB, TV>(n_slices, blk_order, y_nt, sl, xd, val, x, y,
+                                SliceAxpbyDot<T>{SliceAxpby<T>{alpha, beta}, w, yy, partials});
 }
 
 }  // namespace dev

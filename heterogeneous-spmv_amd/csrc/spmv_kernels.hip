@@ -311,4 +311,18 @@ hipError_t launch_spmv_axpby(const DevCSR &A, const DevPlan &dp, int dtype, int 
   return launch_slices_axpby_f32(dp, plan, ab, (const float *)x, (float *)y, stream);
 }
 
+hipError_t launch_spmv_axpby_dot(const DevCSR &A, const DevPlan &dp, int dtype, int val_dtype,
+                                 const LaunchPlan &fwd, const AxpbyScalars &ab, const DotArgs &dot, const void *x,
+                                 void *y, hipStream_t stream, bool reverse) {
+  if (!axpby_fusable(A, dp) || (fwd.kernel != kStream && fwd.kernel != kCsr3)) return hipErrorInvalidValue;
+  LaunchPlan plan = fwd;
+  plan.reverse = reverse;
+  if (dtype == HSPMV_F64 && val_dtype == HSPMV_F32)
+    return launch_slices_axpby_dot_f32v64(dp, plan, ab, dot, (const double *)x, (double *)y, stream);
+  if (dtype != val_dtype) return hipErrorInvalidValue;
+  if (dtype == HSPMV_F64)
+    return launch_slices_axpby_dot_f64(dp, plan, ab, dot, (const double *)x, (double *)y, stream);
+  return launch_slices_axpby_dot_f32(dp, plan, ab, dot, (const float *)x, (float *)y, stream);
+}
+
 }  // namespace hspmv

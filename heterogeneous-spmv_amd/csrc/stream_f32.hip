@@ -11,4 +11,8 @@ hipError_t launch_slices_axpby_f32(const DevPlan &dp, const LaunchPlan &p, const
                                    const float *x, float *y, hipStream_t st) {
   return dev::launch_slices<float, float>(dp, p, x, y, st, &ab);
 }
+hipError_t launch_slices_axpby_dot_f32(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                       const DotArgs &dot, const float *x, float *y, hipStream_t st) {
+  return dev::launch_slices<float, float>(dp, p, x, y, st, &ab, &dot);
+}
 }  // namespace hspmv

@@ -13,4 +13,8 @@ hipError_t launch_slices_axpby_f32v64(const DevPlan &dp, const LaunchPlan &p, co
                                       const double *x, double *y, hipStream_t st) {
   return dev::launch_slices<double, float>(dp, p, x, y, st, &ab);
 }
+hipError_t launch_slices_axpby_dot_f32v64(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                          const DotArgs &dot, const double *x, double *y, hipStream_t st) {
+  return dev::launch_slices<double, float>(dp, p, x, y, st, &ab, &dot);
+}
 }  // namespace hspmv

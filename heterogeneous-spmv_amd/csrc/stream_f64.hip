@@ -11,6 +11,10 @@ hipError_t launch_slices_axpby_f64(const DevPlan &dp, const LaunchPlan &p, const
                                    const double *x, double *y, hipStream_t st) {
   return dev::launch_slices<double, double>(dp, p, x, y, st, &ab);
 }
+hipError_t launch_slices_axpby_dot_f64(const DevPlan &dp, const LaunchPlan &p, const AxpbyScalars &ab,
+                                       const DotArgs &dot, const double *x, double *y, hipStream_t st) {
+  return dev::launch_slices<double, double>(dp, p, x, y, st, &ab, &dot);
+}
 }  // namespace hspmv
 
 #if (HSPMV_DIAG & (8 | 512))

@@ -148,6 +148,8 @@ SWEEP = {"auto": 0, "forward": 1, "alternate": 2}
 # hspmv_set_axpby_path's modes (HSPMV_AXPBY_*) and hspmv_axpby_path's answers
 AXPBY_MODES = {"auto": 0, "two_pass": 1}
 AXPBY_PATHS = {1: "two_pass", 2: "fused"}
+# hspmv_spmv_axpby_dot's `which` (HSPMV_DOT_*)
+DOT_WY, DOT_YY = 1, 2
 CSR3_PLAN_NAMES = {0: None, 1: "aligned", 2: "packed", 3: "ssr", 4: "row_groups"}
 
 
@@ -224,6 +226,13 @@ SIGNATURES = {
     "hspmv_set_axpby_path": (C.c_int, [_H, C.c_int]),
     "hspmv_axpby_path": (C.c_int, [_H]),
     "hspmv_set_y": (C.c_int, [_H, _P]),
+    "hspmv_spmv_axpby_dot": (C.c_int, [_H, C.c_double, C.c_double, C.c_uint]),
+    "hspmv_run_axpby_dot": (C.c_int, [_H, C.c_double, C.c_double, C.c_uint, C.c_int, C.c_int,
+                                      C.POINTER(Timing)]),
+    "hspmv_set_w": (C.c_int, [_H, _P]),
+    "hspmv_bind_w_device": (C.c_int, [_H, _P]),
+    "hspmv_bind_dots_device": (C.c_int, [_H, _P]),
+    "hspmv_get_dots": (C.c_int, [_H, C.POINTER(C.c_double)]),
     "hspmv_synchronize": (C.c_int, [_H]),
     "hspmv_set_sweep": (C.c_int, [_H, C.c_int]),
     "hspmv_block_order": (C.c_int, [C.c_int64, C.c_int32, C.c_int, _P]),

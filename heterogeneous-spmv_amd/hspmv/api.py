@@ -430,6 +430,9 @@ class SpMV:
     single-device handles, fused into the row-slice kernel where the plan is
     the row slices and in two passes otherwise -- ``op.axpby_path`` tells
     which, :meth:`set_axpby_path` forces the two passes; the same bytes.
+    :meth:`spmv_axpby_dot` is that call with w . y and y . y of the y it
+    writes, from the same pass (:meth:`set_w`, :meth:`bind_w_device`,
+    :meth:`bind_dots_device`, :meth:`get_dots`, :meth:`run_axpby_dot`).
     """
 
     def __init__(self, A: CsrMatrix, maps: Optional[Csr3Maps] = None, *, num_gpus: int = 1,
@@ -625,6 +628,64 @@ class SpMV:
         t = _lib.Timing()
         check(lib().hspmv_run_axpby(self._h, float(alpha), float(beta), int(warmup), int(iters), C.byref(t)),
               "hspmv_run_axpby")
+        return {k: getattr(t, k) for k, _ in _lib.Timing._fields_}
+
+    # -- w . y and y . y from the pass that writes y
+    def set_w(self, w: np.ndarray) -> None:
+        """m values into a buffer the handle owns, the w of the next
+        :meth:`spmv_axpby_dot` (hspmv_set_w).  ValueError (before any library
+        call) for another shape than (m,) or a dtype that does not cast
+        ``same_kind`` to ``op.dtype``."""
+        w = np.asarray(w)
+        if w.shape != (self.A.m,):
+            raise ValueError(f"w has shape {w.shape}, expected (m,) = ({self.A.m},)")
+        if not np.can_cast(w.dtype, self.dtype, casting="same_kind"):
+            raise ValueError(f"w has dtype {w.dtype}, which does not cast to {np.dtype(self.dtype)}")
+        w = np.ascontiguousarray(w, dtype=self.dtype)
+        check(lib().hspmv_set_w(self._h, _ptr(w)), "hspmv_set_w")
+
+    def bind_w_device(self, ptr: Optional[int]) -> None:
+        """w = a device array of m ``op.dtype`` entries (hspmv_bind_w_device;
+        x's pointer gives x . A x); None: back to the handle's own."""
+        check(lib().hspmv_bind_w_device(self._h, ptr), "hspmv_bind_w_device")
+
+    def bind_dots_device(self, ptr: Optional[int]) -> None:
+        """The two float64 results {wy, yy} go to this device address from the
+        next call on (hspmv_bind_dots_device); None: the handle's own pair."""
+        check(lib().hspmv_bind_dots_device(self._h, ptr), "hspmv_bind_dots_device")
+
+    @staticmethod
+    def _dot_which(wy: bool, yy: bool) -> int:
+        which = (_lib.DOT_WY if wy else 0) | (_lib.DOT_YY if yy else 0)
+        if not which:
+            raise ValueError("spmv_axpby_dot: ask for wy, yy or both")
+        return which
+
+    def spmv_axpby_dot(self, alpha: float = 1.0, beta: float = 0.0, wy: bool = False, yy: bool = True) -> None:
+        """:meth:`spmv_axpby`, the same bytes of y, and from the same pass
+        ``wy`` = w . y and / or ``yy`` = y . y over the y it stores, summed in
+        float64 in a fixed order (hspmv_spmv_axpby_dot).  Enqueued; the results
+        stay on the device (:meth:`bind_dots_device`), :meth:`get_dots` reads
+        them.  ValueError (before any library call) when neither is asked for."""
+        which = self._dot_which(wy, yy)
+        check(lib().hspmv_spmv_axpby_dot(self._h, float(alpha), float(beta), which), "hspmv_spmv_axpby_dot")
+
+    def get_dots(self):
+        """(wy, yy) of the last :meth:`spmv_axpby_dot` as Python floats, after
+        synchronising the handle's stream (hspmv_get_dots); the one not asked
+        for is 0.0."""
+        d = (C.c_double * 2)()
+        check(lib().hspmv_get_dots(self._h, d), "hspmv_get_dots")
+        return d[0], d[1]
+
+    def run_axpby_dot(self, alpha: float, beta: float, wy: bool = False, yy: bool = True, warmup: int = 5,
+                      iters: int = 20) -> dict:
+        """:meth:`run_axpby`'s protocol over :meth:`spmv_axpby_dot`
+        (hspmv_run_axpby_dot)."""
+        which = self._dot_which(wy, yy)
+        t = _lib.Timing()
+        check(lib().hspmv_run_axpby_dot(self._h, float(alpha), float(beta), which, int(warmup), int(iters),
+                                        C.byref(t)), "hspmv_run_axpby_dot")
         return {k: getattr(t, k) for k, _ in _lib.Timing._fields_}
 
     @property

@@ -58,7 +58,10 @@ extern "C" {
  * HSPMV_VALUES_DEVICE, and for column-sorted handles hspmv_create_updatable,
  * hspmv_can_update_values; the general form y = alpha A x + beta y:
  * hspmv_spmv_axpby, hspmv_run_axpby, hspmv_set_y, hspmv_set_axpby_path,
- * hspmv_axpby_path -- functions only, no struct grew. */
+ * hspmv_axpby_path; its dot products from the same pass:
+ * hspmv_spmv_axpby_dot, hspmv_run_axpby_dot, hspmv_set_w,
+ * hspmv_bind_w_device, hspmv_bind_dots_device, hspmv_get_dots -- functions
+ * only, no struct grew. */
 
 /* ---------------------------------------------------------------- status */
 #define HSPMV_OK 0
@@ -608,8 +611,7 @@ int hspmv_synchronize(hspmv_handle *h);
  * the same device pointer.  HSPMV_E_STATE: x not set.
  *
  * Not covered: sharded handles; hspmv_mm_*; the epilogue inside the chunked,
- * vector and column-sorted kernels (they take the two-pass path); a fused dot
- * product. */
+ * vector and column-sorted kernels (they take the two-pass path). */
 #define HSPMV_AXPBY_AUTO 0
 #define HSPMV_AXPBY_TWO_PASS 1
 #define HSPMV_AXPBY_PATH_TWO_PASS 1
@@ -621,6 +623,74 @@ int hspmv_axpby_path(hspmv_handle *h);
  * use -- its own buffer, or the array bound by hspmv_bind_y_device -- as
  * hspmv_set_x does for x: consumed before return.  Single-device handles. */
 int hspmv_set_y(hspmv_handle *h, const void *y_host);
+
+/* hspmv_spmv_axpby and, from the pass that writes y, the two dot products an
+ * iterative solver takes next: p . Ap, the residual's r . r, BiCGStab's
+ * r0 . Ap, t . s and t . t, the Rayleigh quotient x . A x -- without a further
+ * launch and a further read of y for each.
+ *
+ * Contract.  y is byte for byte what hspmv_spmv_axpby(h, alpha, beta) writes:
+ * the three roundings, beta_T == 0 never reads y, alpha = 1 and beta = 0 give
+ * hspmv_spmv's bytes, and the sweep phase advances once per call.  With y_new
+ * the values stored (in T, the vector dtype) and `which` a mask of
+ * HSPMV_DOT_WY and HSPMV_DOT_YY (0 and any other bit: HSPMV_E_INVALID):
+ *     dots[0] = sum over the m rows of (double)w[r] * (double)y_new[r]   HSPMV_DOT_WY
+ *     dots[1] = sum over the m rows of (double)y_new[r]^2                HSPMV_DOT_YY
+ * Products and sums are double for every handle (an fp32 handle's products
+ * are then exact); a slot `which` does not name is written as 0.0; without
+ * HSPMV_DOT_WY w is never read and need not exist.  Non-finite values
+ * propagate as IEEE 754 says (a NaN of y_old under beta = 0 reaches neither y
+ * nor the dots).
+ *
+ * Order.  The summation order is fixed per handle and path: it depends on
+ * neither the sweep direction, nor the order the grid's workgroups run in,
+ * nor earlier calls, and no floating-point atomic is used.  The same handle,
+ * x, w and y_old give the same 16 bytes on every call.  The two paths (below)
+ * sum in different orders: their dots may differ in the last bits, each
+ * within (m + 4) 2^-53 sum |terms| of the exact sum.
+ *
+ * Where the results live.  On the device: 2 doubles {wy, yy} the handle owns,
+ * or the array bound by hspmv_bind_dots_device (2 doubles on the handle's
+ * device, 8-byte aligned; NULL: back to the handle's own).  The call is
+ * enqueued on the handle's stream with no host synchronisation, like
+ * hspmv_spmv: work that follows on that stream reads the bound array without
+ * a round trip.  hspmv_get_dots synchronises the stream and copies the pair
+ * the last dot call wrote.
+ *
+ * w.  m entries of the vector dtype: hspmv_set_w copies them from host memory
+ * into a buffer the handle owns and uses that; hspmv_bind_w_device uses the
+ * caller's device array (NULL: back to the handle's own).  w[r] is read only
+ * by the lane or thread that owns row r.  w may be x (p . Ap; the caller
+ * vouches for m entries); w the same pointer as y is HSPMV_E_INVALID: ask for
+ * HSPMV_DOT_YY.
+ *
+ * Two paths, as for hspmv_spmv_axpby and chosen by the same rule
+ * (hspmv_axpby_path, hspmv_set_axpby_path): fused, the slice kernel forms the
+ * terms from the values it stores and each wave writes its slice's pair;
+ * two-pass, the elementwise kernel does and each workgroup writes its pair.
+ * One small kernel of a fixed launch shape then adds the pairs.
+ *
+ * Refusals, all before any launch, y and the dots untouched.
+ * HSPMV_E_INVALID: a NULL handle; a sharded handle (the five other calls
+ * below refuse it too); x and y the same device pointer; w and y the same; a
+ * bad `which`.  HSPMV_E_STATE: x not set; HSPMV_DOT_WY with no w set or
+ * bound; hspmv_get_dots before any dot call.
+ *
+ * Device memory: the handle's own w, the partial pairs and the own result are
+ * allocated by the first call that needs each, counted in
+ * hspmv_info.device_bytes from then on and freed with the handle; later calls
+ * allocate nothing.
+ *
+ * Not covered: sharded handles; hspmv_mm_*; the dot epilogue inside the
+ * chunked, vector and column-sorted kernels (they take the two-pass path); a
+ * single-launch finish; bitwise equality of the two paths' dots. */
+#define HSPMV_DOT_WY 1u
+#define HSPMV_DOT_YY 2u
+int hspmv_spmv_axpby_dot(hspmv_handle *h, double alpha, double beta, unsigned which);
+int hspmv_set_w(hspmv_handle *h, const void *w_host);
+int hspmv_bind_w_device(hspmv_handle *h, const void *w_dev);
+int hspmv_bind_dots_device(hspmv_handle *h, double *dots_dev);
+int hspmv_get_dots(hspmv_handle *h, double out[2]);
 
 /* Sweep direction of the STREAM / CSR3 row kernel (the row-slice kernel
  * included) from one SpMV of this handle to the next.  A matrix larger than
@@ -660,6 +730,11 @@ int hspmv_run(hspmv_handle *h, int warmup, int iters, hspmv_timing *out);
  * stay finite over warmup + iters calls.  gflops = 2 nnz / t_min; gbps_alg
  * counts hspmv_alg_bytes plus, for beta != 0, the m elements of y_old read. */
 int hspmv_run_axpby(hspmv_handle *h, double alpha, double beta, int warmup, int iters, hspmv_timing *out);
+/* The same over hspmv_spmv_axpby_dot(h, alpha, beta, which), with its
+ * refusals; gbps_alg adds the m elements of w under HSPMV_DOT_WY.  The dots
+ * are those of the last iteration. */
+int hspmv_run_axpby_dot(hspmv_handle *h, double alpha, double beta, unsigned which, int warmup, int iters,
+                        hspmv_timing *out);
 
 /* y (m entries of dtype) -> host; gathers the shards of a multi-GPU handle
  * (getY, csrk.cu:110-113). */
